@@ -16,7 +16,11 @@ all-reduce time.  `--gpus N` without a torchrun environment
 re-executes itself through `python -m torch.distributed.run --nproc-per-node N` (as the reference's launch.py:89-108
 does with torchrun); under torchrun WORLD_SIZE must equal --gpus.
 
-Rank 0 prints ONE JSON line.  `value` = volumes / s over all GPUs.  `roofline` = the selective-scan forward at
+Rank 0 prints ONE JSON line.  `value` = volumes / s over all GPUs, `ms_per_step` = milliseconds per timed step.  A plain run
+sets up, warms up, times the --steps steps and prints the line; `--dump-outputs DIR` also writes what the last timed step computed
+(loss, parameters and gradients after it, float32 .npy; the inputs and initial weights are seeded, so two builds compare output
+for output).  Everything below, and the rocm-smi clock / power readings and the N > 1 side measurements, runs with `--full` only
+(the `--no-*` switches trim it).  `roofline` = the selective-scan forward at
 SegMamba's largest stage (B=2, D=96, N=16, L=64^3, same dtype as the step): algorithmic bytes (SURVEY.md §8d:
 e*B*L*(5D+2N)) / its measured duration (HIP events on the launch stream), against 8 TB/s HBM; the backward, the
 three-directions-per-launch form the training step uses and `valu` (the same launch against the instruction-issue bound that
@@ -73,6 +77,13 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--size", type=int, default=128, help="edge of the cubic volume (128 = the BASELINE config)")
     p.add_argument("--batch", type=int, default=2, help="volumes per GPU")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beyond the headline step time: inference, roofline, launch forms, drop-in loop, "
+                        "BASELINE configs 1 / 4, CPU baseline, clock / power readings, the N > 1 side measurements (the --no-* "
+                        "switches below apply within it)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed (loss, parameters and gradients after the step; "
+                        "a fixed seeded sample of the latter two) as DIR/<name>.npy, float32")
     p.add_argument("--no-roofline", action="store_true")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-configs", action="store_true", help="skip the BASELINE config 1 / config 4 measurements")
@@ -82,7 +93,12 @@ def parse():
     p.add_argument("--cpu-dry-run", action="store_true",
                    help="plumbing check without a GPU: gloo, CPU tensors, a tiny SegMamba on the CPU emulation of the kernels "
                         "(tests/emu); the printed value is NOT a measurement")
-    return p.parse_args()
+    args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
+    if args.warmup < 0:
+        p.error("--warmup must not be negative")
+    return args
 
 
 def self_launch(args):
@@ -567,6 +583,29 @@ def cpu_baseline(full=False):
     return out
 
 
+DUMP_SAMPLE = 1 << 22     # elements kept of a longer array: 16 MB of float32 each, 32 MB for parameters + gradients
+
+
+def dump_outputs(dirname, state, loss):
+    """--dump-outputs: what the timed step hands its caller after the last step - the loss it returns, the parameters the
+    optimizer left and the gradients of that step, in model.parameters() order - as float32 .npy files.  Longer than
+    DUMP_SAMPLE elements: the same seeded, sorted sample of indices for both (the same for every run of the same model)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    model = state.model.module if hasattr(state.model, "module") else state.model
+    params = list(model.parameters())
+    with torch.no_grad():
+        flat_p = torch.cat([p.detach().float().reshape(-1) for p in params])
+        flat_g = torch.cat([(p.grad.detach() if p.grad is not None else torch.zeros_like(p)).float().reshape(-1) for p in params])
+        n = flat_p.numel()
+        if n > DUMP_SAMPLE:
+            idx = torch.randint(0, n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).unique().to(flat_p.device)
+            flat_p, flat_g = flat_p[idx], flat_g[idx]
+        arrays = {"loss": loss.detach().float().reshape(1), "params": flat_p, "grads": flat_g}
+        for name, t in arrays.items():
+            np.save(os.path.join(dirname, name + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
 _T0 = time.time()
 
 
@@ -613,9 +652,9 @@ def main():
 
     from segmamba_amd.trainer import DDP_SETTINGS, SyntheticBraTS, build_training_state, train_step
     model = None
+    torch.manual_seed(0)                                   # the same initial weights every run (the data is seeded below)
     if dry:
         from segmamba_amd.segmamba import SegMamba
-        torch.manual_seed(0)
         model = SegMamba(in_chans=4, out_chans=4, depths=[1, 1, 1, 1], feat_size=[48, 16, 16, 32], hidden_size=32)
         args.size, args.batch = 32, 1
     state = build_training_state(device, distributed, local_rank, model=model)
@@ -653,10 +692,11 @@ def main():
     if distributed:
         dist.barrier()
     sync()
-    state_before = gpu_state(local_rank) if (rank == 0 and not dry) else {}
+    extras = rank == 0 and not dry and args.full          # clock / power readings: --full only
+    state_before = gpu_state(local_rank) if extras else {}
     state_during = {}
     sampler = None
-    if rank == 0 and not dry:                              # one rocm-smi reading WHILE the timed steps run (the GPU idles down within
+    if extras:                                             # one rocm-smi reading WHILE the timed steps run (the GPU idles down within
         import threading                                   # milliseconds of the final synchronize): a thread, the host loop only replays a graph
 
         def _sample():
@@ -685,9 +725,11 @@ def main():
         "launch": "graph replay" if state.graphed is not None else "eager",
         "recompute": os.environ.get("SEGM_RECOMPUTE", "0"),
         "reference_published_mb": {"training": 17976, "inference": 6279, "source": "reference README.md:15-16 (Table 5), batch and GPU not stated"}}
+    if args.dump_outputs and rank == 0:                    # behind the memory figures: its copies are not the step's
+        dump_outputs(args.dump_outputs, state, loss)
     if sampler is not None:
         sampler.join(timeout=30)
-    state_after = gpu_state(local_rank) if (rank == 0 and not dry) else {}
+    state_after = gpu_state(local_rank) if extras else {}
     rank_ms = [elapsed / args.steps * 1e3]
     allreduce_ms = exposed_ms = other_form = None
     overlapped = state.exchange is not None and not state.exchange.suspended      # the form the timed region ran
@@ -700,7 +742,7 @@ def main():
         dist.all_gather(every, t)
         rank_ms = [float(x.item()) / args.steps * 1e3 for x in every]
         elapsed = max(float(x.item()) for x in every)                # MAX over ranks
-        if state.flat and not dry:                                   # the exchange step on its own: one all-reduce of the flat gradients
+        if state.flat and not dry and args.full:                     # the exchange step on its own: one all-reduce of the flat gradients
             try:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 dist.all_reduce(state.bank.flat_grad)
@@ -754,11 +796,14 @@ def main():
                        # (param_bank.py), 128^3 volumes with a padded channel stride (ops_raw.volume_empty)
                        "param_bank": state.bank is not None, "volume_pad": os.environ.get("SEGM_VOLUME_PAD", "1") == "1",
                        "flat_gradients": state.flat, "launch": graph_note,
-                       "command": "python bench.py --gpus %d --steps %d --warmup %d" % (world, args.steps, args.warmup),
-                       "gpu_state": {"before_timed_loop": state_before, "during_timed_loop": state_during, "after_timed_loop": state_after,
-                                     "source": "rocm-smi --showclocks --showpower --showtemp --showperflevel, rank 0's GPU"}},
+                       "command": "python bench.py --gpus %d --steps %d --warmup %d%s" % (world, args.steps, args.warmup,
+                                                                                          " --full" if args.full else "")},
         }
-        if not args.no_roofline and not dry:
+        if extras:
+            out["config"]["gpu_state"] = {"before_timed_loop": state_before, "during_timed_loop": state_during,
+                                          "after_timed_loop": state_after,
+                                          "source": "rocm-smi --showclocks --showpower --showtemp --showperflevel, rank 0's GPU"}
+        if args.full and not args.no_roofline and not dry:
             out["inference"] = inference_rate(state, device, args.size)
             out["roofline"] = scan_roofline(torch.bfloat16, device)
             out["roofline_fp32"] = scan_roofline(torch.float32, device)
@@ -784,7 +829,7 @@ def main():
                         out[key] = fn(device)
                     except Exception as e:                  # noqa: BLE001 - the step's number must not be lost to a side measurement
                         out[key] = {"error": f"{type(e).__name__}: {str(e)[:300]}"}
-        if not args.no_cpu_baseline and world == 1 and not dry:       # the host-core baseline is reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and not dry:   # the host-core baseline is reported at N = 1 only
             _stamp("configs done")
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_full)
             _stamp("cpu_baseline done")
@@ -809,8 +854,8 @@ def main():
     # all-reduce behind it - for three steps, so that the line carries both forms.  It cannot cost the measurement: every rank
     # attempts the capture on its own (no collective inside), ONE all-reduce (MIN) of a success flag decides for all of them whether
     # the extra steps run, and a watchdog thread ends the job cleanly - rank 0 prints the finished line first - if this block does
-    # not come back within SEGM_BENCH_OTHER_FORM_TIMEOUT_S seconds (default 90).  SEGM_BENCH_OTHER_FORM=0 skips it.
-    if distributed and not dry and state is not None and state.exchange is not None and state.graphed is None and not args.no_graph \
+    # not come back within SEGM_BENCH_OTHER_FORM_TIMEOUT_S seconds (default 90).  SEGM_BENCH_OTHER_FORM=0 skips it; --full only.
+    if args.full and distributed and not dry and state is not None and state.exchange is not None and state.graphed is None and not args.no_graph \
             and os.environ.get("SEGM_BENCH_OTHER_FORM", "1") == "1" and state.exchange.fallback_reason is None:
         import threading
         done = threading.Event()

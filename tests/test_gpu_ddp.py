@@ -17,7 +17,7 @@ def _bench_line(extra_env, port):
     env = dict(os.environ, SEGM_FORCE_DDP="1", HSA_ENABLE_IPC_MODE_LEGACY="0", **extra_env)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--size", "64",
-           "--no-cpu-baseline", "--no-roofline", "--no-configs"]
+           "--full", "--no-cpu-baseline", "--no-roofline", "--no-configs"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

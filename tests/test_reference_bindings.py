@@ -1,112 +1,105 @@
-"""INTEGRATION.md section B, executed: the REFERENCE's own `mamba_ssm/ops/selective_scan_interface.py` running on top of
-`segmamba_amd.native_stubs.{selective_scan_cuda, causal_conv1d_cuda}` (the two module names it imports, :9-11).
+"""`segmamba_amd.native_stubs.{selective_scan_cuda, causal_conv1d_cuda}` - the two native module names
+the reference's `mamba_ssm/ops/selective_scan_interface.py` imports (:9-11) - driven with the call sequences of that file's
+autograd Functions (SelectiveScanFn :36-67, MambaInnerFnNoOutProj :155-289), against what the reference's own
+`selective_scan_ref` / `mamba_inner_ref` computed on the same inputs (tests/golden/make_golden.py):
 
-  * here (build container: /root/reference present, no GPU): the reference file is imported unchanged, the stubs are bound to
-    the CPU emulation build of the kernels, and the reference's autograd Functions `selective_scan_fn` and
-    `mamba_inner_fn_no_out_proj` are compared - output and every gradient - with the reference's own `selective_scan_ref` /
-    `mamba_inner_ref`;
-  * on the GPU box (-m gpu; no /root/reference there): the stubs are driven with the exact call sequences of those
-    Functions (selective_scan_interface.py:36-67 and :213-247) on the HIP library and compared with the oracle.
+  * without a GPU: on the CPU emulation build of the kernels (tests/emu), output and every gradient;
+  * on the GPU (-m gpu): on the HIP library, against the oracle, with the in-place / recompute variants of the backward.
 """
-import os
-import sys
-import types
-
 import pytest
 import torch
-
-REF = "/root/reference"
-
-
-def _load_reference_interface():
-    """the reference's selective_scan_interface module with ITS native imports resolved to our stubs"""
-    from segmamba_amd import native_stubs
-    native_stubs.install()
-    saved = {k: sys.modules.get(k) for k in ("mamba_ssm", "mamba_ssm.ops", "mamba_ssm.ops.selective_scan_interface",
-                                              "causal_conv1d", "causal_conv1d.causal_conv1d_interface")}
-    for k in saved:
-        sys.modules.pop(k, None)
-    pkg = types.ModuleType("mamba_ssm")
-    pkg.__path__ = [os.path.join(REF, "mamba", "mamba_ssm")]       # skip mamba_ssm/__init__.py (LM imports)
-    sys.modules["mamba_ssm"] = pkg
-    sys.path.insert(0, os.path.join(REF, "causal-conv1d"))
-    try:
-        import mamba_ssm.ops.selective_scan_interface as ssi       # the reference's file, unchanged
-    finally:
-        sys.path.pop(0)
-    return ssi, saved
+import torch.nn.functional as F
 
 
-def _restore(saved):
-    for k, v in saved.items():
-        sys.modules.pop(k, None)
-        if v is not None:
-            sys.modules[k] = v
-    for k in ("selective_scan_cuda", "causal_conv1d_cuda"):
-        sys.modules.pop(k, None)
+class _ScanFn(torch.autograd.Function):
+    """the native calls of SelectiveScanFn: fwd -> (out, x, out_z); bwd(..., dout, x, out, dz=None, softplus, False)"""
+
+    @staticmethod
+    def forward(ctx, u, delta, A, B, C, D, z, delta_bias):
+        from segmamba_amd.native_stubs import selective_scan_cuda
+        if B.dim() == 3:                                                  # "b dstate l -> b 1 dstate l"
+            B, C = B.unsqueeze(1).contiguous(), C.unsqueeze(1).contiguous()
+            ctx.squeeze = True
+        else:
+            ctx.squeeze = False
+        out, x, out_z = selective_scan_cuda.fwd(u, delta, A, B, C, D, z, delta_bias, True)
+        ctx.save_for_backward(u, delta, A, B, C, D, z, delta_bias, x, out)
+        return out_z, x[:, :, -1, 1::2]                                  # last state: the odd entries of the final checkpoint
+
+    @staticmethod
+    def backward(ctx, dout, dlast):
+        from segmamba_amd.native_stubs import selective_scan_cuda
+        u, delta, A, B, C, D, z, delta_bias, x, out = ctx.saved_tensors
+        du, ddelta, dA, dB, dC, dD, ddb, dz = selective_scan_cuda.bwd(u, delta, A, B, C, D, z, delta_bias, dout.contiguous(), x,
+                                                                        out, None, True, False)
+        if ctx.squeeze:
+            dB, dC = dB.squeeze(1), dC.squeeze(1)
+        return du, ddelta, dA, dB, dC, dD, dz, ddb
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="needs the reference tree (build container only)")
-def test_reference_python_on_the_stub_modules(monkeypatch):
+class _ConvFn(torch.autograd.Function):
+    """the native calls of the depthwise causal convolution with SiLU: causal_conv1d_fwd / causal_conv1d_bwd(dx=None)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        from segmamba_amd.native_stubs import causal_conv1d_cuda
+        ctx.save_for_backward(x, weight, bias)
+        return causal_conv1d_cuda.causal_conv1d_fwd(x, weight, bias, True)
+
+    @staticmethod
+    def backward(ctx, dout):
+        from segmamba_amd.native_stubs import causal_conv1d_cuda
+        x, weight, bias = ctx.saved_tensors
+        dx, dw, db = causal_conv1d_cuda.causal_conv1d_bwd(x, weight, bias, dout.contiguous(), None, True)
+        return dx, dw, db
+
+
+def _inner_no_out_proj(xz, conv_w, conv_b, x_proj_w, dt_proj_w, A, D, delta_bias):
+    """MambaInnerFnNoOutProj's data flow around the two native modules (the projections as torch ops)"""
+    L_ = xz.shape[-1]
+    R_, N_ = dt_proj_w.shape[1], A.shape[1]
+    x, z = xz.chunk(2, dim=1)
+    conv = _ConvFn.apply(x.contiguous(), conv_w[:, 0], conv_b)
+    x_dbl = F.linear(conv.transpose(1, 2).reshape(-1, conv.shape[1]), x_proj_w)                    # (b l) (r + 2n)
+    delta = (dt_proj_w @ x_dbl[:, :R_].t()).reshape(-1, xz.shape[0], L_).transpose(0, 1).contiguous()   # b d l
+    Bm = x_dbl[:, R_:R_ + N_].reshape(xz.shape[0], L_, N_).transpose(1, 2).contiguous()             # b n l
+    Cm = x_dbl[:, R_ + N_:].reshape(xz.shape[0], L_, N_).transpose(1, 2).contiguous()
+    return _ScanFn.apply(conv, delta, A, Bm, Cm, D, z.contiguous(), delta_bias)[0]
+
+
+def _check_grads(leaves, f, names):
+    for t, name in zip(leaves, names):
+        ref = f["d" + name]
+        scale = max(1.0, float(ref.abs().max()))
+        assert (t.grad - ref).abs().max() <= 1e-3 * scale, name
+
+
+def test_stub_modules_with_the_reference_call_sequences_on_the_emulator(monkeypatch):
     from tests import emu_util
+    from tests import helpers as H
     if not emu_util.emu_available():
         pytest.skip("no host clang for the emulation build")
     from segmamba_amd import lib as L
     monkeypatch.setattr(L, "_lib", emu_util.emu_lib())
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    ssi, saved = _load_reference_interface()
-    try:
-        assert ssi.__file__.startswith(REF)
-        g = torch.Generator().manual_seed(0)
-        # --- standalone op: reference test distributions (mamba/tests/ops/test_selective_scan.py:53-88), G = 1 and 2
-        for G in (1, 2):
-            B_, D_, N_, L_ = 2, 8, 16, 200
-            A = (-0.5 * torch.rand(D_, N_, generator=g)).requires_grad_()
-            shape = (B_, N_, L_) if G == 1 else (B_, G, N_, L_)
-            Bm, Cm = (torch.randn(*shape, generator=g).requires_grad_() for _ in range(2))
-            Dv = torch.randn(D_, generator=g).requires_grad_()
-            z, u = (torch.randn(B_, D_, L_, generator=g).requires_grad_() for _ in range(2))
-            db = (0.5 * torch.rand(D_, generator=g)).requires_grad_()
-            delta = (0.5 * torch.rand(B_, D_, L_, generator=g)).requires_grad_()
-            leaves = [u, delta, A, Bm, Cm, Dv, z, db]
-            ref_leaves = [t.detach().clone().requires_grad_() for t in leaves]
-            out, last = ssi.selective_scan_fn(*leaves, delta_softplus=True, return_last_state=True)
-            out_ref, last_ref = ssi.selective_scan_ref(*ref_leaves, delta_softplus=True, return_last_state=True)
-            assert torch.allclose(out, out_ref, rtol=1e-3, atol=1e-3)
-            assert torch.allclose(last, last_ref, rtol=1e-3, atol=1e-3)
-            gout = torch.randn(out.shape, generator=g)
-            out.backward(gout)
-            out_ref.backward(gout)
-            for a, b, name in zip(leaves, ref_leaves, "u delta A B C D z delta_bias".split()):
-                scale = max(1.0, float(b.grad.abs().max()))
-                assert (a.grad - b.grad).abs().max() <= 1e-3 * scale, name
-        # --- the fused function SegMamba uses (reference :155-289) against mamba_inner_ref without the out-projection
-        B_, D_, N_, L_, R_ = 2, 16, 16, 96, 2
-        xz = torch.randn(B_, 2 * D_, L_, generator=g).requires_grad_()
-        conv_w = (0.5 * torch.randn(D_, 1, 4, generator=g)).requires_grad_()
-        conv_b = (0.1 * torch.randn(D_, generator=g)).requires_grad_()
-        xw = (0.3 * torch.randn(R_ + 2 * N_, D_, generator=g)).requires_grad_()
-        dtw = (0.3 * torch.randn(D_, R_, generator=g)).requires_grad_()
-        A = (-0.5 * torch.rand(D_, N_, generator=g)).requires_grad_()
-        Dv = torch.randn(D_, generator=g).requires_grad_()
-        db = (0.5 * torch.rand(D_, generator=g)).requires_grad_()
-        leaves = [xz, conv_w, conv_b, xw, dtw, A, Dv, db]
-        ref_leaves = [t.detach().clone().requires_grad_() for t in leaves]
-        y = ssi.mamba_inner_fn_no_out_proj(xz, conv_w, conv_b, xw, dtw, A, None, None, Dv, db, None, None, True)
-        import causal_conv1d.causal_conv1d_interface as cci
-        monkeypatch.setattr(ssi, "causal_conv1d_fn", cci.causal_conv1d_ref)
-        r = ref_leaves
-        y_ref = ssi.mamba_inner_ref(r[0], r[1], r[2], r[3], r[4], torch.eye(D_), None, r[5], None, None, r[6], r[7], None, None,
-                                    True).transpose(1, 2)
-        assert torch.allclose(y, y_ref, rtol=1e-3, atol=1e-3)
-        gy = torch.randn(y.shape, generator=g)
-        y.backward(gy)
-        y_ref.backward(gy)
-        for a, b, name in zip(leaves, ref_leaves, "xz conv_w conv_b x_proj_w dt_proj_w A D delta_bias".split()):
-            scale = max(1.0, float(b.grad.abs().max()))
-            assert (a.grad - b.grad).abs().max() <= 1e-3 * scale, name
-    finally:
-        _restore(saved)
+    # --- standalone op at the reference test's distributions, G = 1 and 2
+    for G in (1, 2):
+        f = H.load_golden(f"scan_L256_G{G}.npz")
+        names = ("u", "delta", "A", "B", "C", "D", "z", "delta_bias")
+        leaves = [f[k].clone().requires_grad_() for k in names]
+        out, last = _ScanFn.apply(*leaves)
+        assert torch.allclose(out, f["out"], rtol=1e-3, atol=1e-3)
+        assert torch.allclose(last, f["last_state"], rtol=1e-3, atol=1e-3)
+        out.backward(f["g"])
+        _check_grads(leaves, f, names)
+    # --- the fused function SegMamba uses, against mamba_inner_ref without the out-projection
+    f = H.load_golden("inner_no_out_proj.npz")
+    names = ("xz", "conv_w", "conv_b", "x_proj_w", "dt_proj_w", "A", "D", "delta_bias")
+    leaves = [f[k].clone().requires_grad_() for k in names]
+    y = _inner_no_out_proj(*leaves)
+    assert torch.allclose(y, f["out"], rtol=1e-3, atol=1e-3)
+    y.backward(f["g"])
+    _check_grads(leaves, f, names)
 
 
 @pytest.mark.gpu
