@@ -802,6 +802,87 @@ typedef struct segm_channel_sum_args {
 size_t segm_channel_sum_workspace_bytes(int32_t batch, int32_t channels, int64_t spatial);
 int segm_channel_sum(const segm_channel_sum_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation: Dice and Hausdorff distances of label volumes (additive to ABI 10).
+ * Replaces  medpy.metric.binary.dc / hd95 as called per region by reference 5_compute_metrics.py:24-38
+ *           (`cal_metric` / `each_cases_metric`), and the counts behind the validation Dice of 3_train.py:82-119.
+ *
+ * Label volumes are (depth, height, width) uint8, contiguous, x fastest.  A REGION is a set of label values, given by a 256-entry
+ * uint8 table in device memory: bit r of table[l] says that label l belongs to region r (up to SEGM_METRICS_MAX_REGIONS at once;
+ * BraTS: TC = {1, 3}, WT = {1, 2, 3}, ET = {3}, 5_compute_metrics.py:40-46).  Volumes of region bits ("bit planes": bit r of a
+ * byte = region r) are what the three entries hand to one another.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_METRICS_MAX_REGIONS 8
+#define SEGM_METRICS_MAX_PLANES 16                 /* planes per distance-transform call, items per border-distance call */
+#define SEGM_METRICS_MAX_VOXELS (1 << 30)
+#define SEGM_EDT_MAX_LINE 256                      /* largest depth, height and width of the distance transform */
+
+/* One pass over a prediction and a ground truth.  Per region r:
+ *   counts[q * 8 + r], q = 0 .. 4:  |P|, |G|, |P and G|, |border of P|, |border of G|   (40 int64, all OVERWRITTEN; unused regions 0)
+ *   border_pred / border_gt: bit r set iff the voxel is in the region and one of its six face neighbours is not, everything outside
+ *   the volume counting as not in the region (scipy's binary_erosion with the connectivity-1 cross and border_value 0, which is
+ *   medpy's `mask ^ erosion(mask)`).
+ * Per-workgroup partial counts in the workspace, added by a second kernel: integers, no atomics.
+ * depth * height * width <= SEGM_METRICS_MAX_VOXELS. */
+typedef struct segm_seg_regions_args {
+    int32_t depth, height, width, reserved;
+    const uint8_t* pred;
+    const uint8_t* gt;
+    const uint8_t* table;          /* 256 bytes, device memory */
+    uint8_t* border_pred;          /* (depth, height, width) */
+    uint8_t* border_gt;
+    int64_t* counts;               /* 40 values, device memory */
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_seg_regions_args;
+size_t segm_seg_regions_workspace_bytes(int64_t voxels);
+int segm_seg_regions(const segm_seg_regions_args* args);
+
+/* Exact squared Euclidean distance transform of a batch of bit planes:
+ *   out[p][z][y][x] = min over the voxels v whose bit plane_bit[p] is set in volume plane_volume[p] of
+ *                     (spacing_z dz)^2 + (spacing_y dy)^2 + (spacing_x dx)^2
+ * i.e. scipy.ndimage.distance_transform_edt(~plane, sampling = spacing) ** 2.  Separable, three passes (x, then y, then z; the y and z
+ * passes in place in `out`), brute-force min-plus over the whole line held in LDS: exact and deterministic.
+ * fp32 = 0: int32 arithmetic and output, spacing must be (1, 1, 1) (else SEGM_E_DTYPE); a plane without a set bit gives INT32_MAX.
+ * fp32 = 1: fp32 arithmetic and output, any positive spacing; a plane without a set bit gives +inf.
+ * depth, height, width in [1, SEGM_EDT_MAX_LINE] (else SEGM_E_SHAPE); n_volumes, n_planes in [1, SEGM_METRICS_MAX_PLANES]. */
+typedef struct segm_edt_sq_args {
+    int32_t depth, height, width;
+    int32_t n_volumes, n_planes, fp32;
+    float spacing_z, spacing_y, spacing_x;
+    int32_t reserved;
+    int32_t plane_volume[SEGM_METRICS_MAX_PLANES];
+    int32_t plane_bit[SEGM_METRICS_MAX_PLANES];
+    const uint8_t* volumes;        /* (n_volumes, depth, height, width) */
+    void* out;                     /* (n_planes, depth, height, width) int32 or fp32 */
+    void* stream;
+} segm_edt_sq_args;
+int segm_edt_sq(const segm_edt_sq_args* args);
+
+/* Distances from border voxels to another border, from the squared distance transform of that other border.  Item i:
+ *   out[out_offset[i] + k] = sqrt(edt[edt_plane[i]][v_k]),  v_k = the k-th voxel (in memory order) whose bit border_bit[i] is set in
+ *   volume border_volume[i],  k < out_count[i]
+ * (medpy's `__surface_distances`: `distance_transform_edt(~reference_border)[result_border]`).  out_count[i] is the border count
+ * that the region pass reported; out_offset[i] + out_count[i] <= out_capacity.  The order is fixed: per-workgroup counts, an
+ * exclusive scan of them (both in the workspace), then the write - no atomics.  `edt` is int32 (fp32 = 0) or fp32 (fp32 = 1). */
+typedef struct segm_border_distances_args {
+    int64_t voxels;                /* depth * height * width <= SEGM_METRICS_MAX_VOXELS */
+    int32_t n_volumes, n_planes, n_items, fp32;
+    int32_t border_volume[SEGM_METRICS_MAX_PLANES];
+    int32_t border_bit[SEGM_METRICS_MAX_PLANES];
+    int32_t edt_plane[SEGM_METRICS_MAX_PLANES];
+    int64_t out_offset[SEGM_METRICS_MAX_PLANES];
+    int64_t out_count[SEGM_METRICS_MAX_PLANES];
+    int64_t out_capacity;          /* elements of `out` */
+    const uint8_t* borders;        /* (n_volumes, voxels) bit planes */
+    const void* edt;               /* (n_planes, voxels) */
+    float* out;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_border_distances_args;
+size_t segm_border_distances_workspace_bytes(int64_t voxels, int32_t n_items);
+int segm_border_distances(const segm_border_distances_args* args);
+
 
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);

@@ -296,6 +296,7 @@ EXPORTS = (
     "segm_causal_conv1d_update", "segm_selective_state_update", "segm_linear_rows", "segm_pointwise_cf", "segm_stem_conv_fwd",
     "segm_stem_conv_wgrad", "segm_stem_conv_wgrad_workspace_bytes", "segm_stem_conv_wgrad_workspace_bytes2", "segm_wgrad_gemm", "segm_wgrad_gemm_workspace_bytes",
     "segm_skinny_tn", "segm_skinny_tn_workspace_bytes", "segm_channel_sum", "segm_channel_sum_workspace_bytes", "segm_selective_scan_regular_shape",
+    "segm_seg_regions", "segm_seg_regions_workspace_bytes", "segm_edt_sq", "segm_border_distances", "segm_border_distances_workspace_bytes",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -310,6 +311,32 @@ class ChannelSumArgs(C.Structure):
     _fields_ = [("x", C.c_void_p), ("stride_batch", C.c_int64), ("stride_channel", C.c_int64), ("spatial", C.c_int64),
                 ("batch", C.c_int32), ("channels", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32),
                 ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+METRICS_MAX_REGIONS, METRICS_MAX_PLANES, METRICS_MAX_VOXELS, EDT_MAX_LINE = 8, 16, 1 << 30, 256       # SEGM_METRICS_* / SEGM_EDT_MAX_LINE
+
+
+class SegRegionsArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("pred", C.c_void_p), ("gt", C.c_void_p), ("table", C.c_void_p), ("border_pred", C.c_void_p), ("border_gt", C.c_void_p),
+                ("counts", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class EdtSqArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("n_volumes", C.c_int32), ("n_planes", C.c_int32), ("fp32", C.c_int32),
+                ("spacing_z", C.c_float), ("spacing_y", C.c_float), ("spacing_x", C.c_float), ("reserved", C.c_int32),
+                ("plane_volume", C.c_int32 * METRICS_MAX_PLANES), ("plane_bit", C.c_int32 * METRICS_MAX_PLANES),
+                ("volumes", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class BorderDistancesArgs(C.Structure):
+    _fields_ = [("voxels", C.c_int64), ("n_volumes", C.c_int32), ("n_planes", C.c_int32), ("n_items", C.c_int32), ("fp32", C.c_int32),
+                ("border_volume", C.c_int32 * METRICS_MAX_PLANES), ("border_bit", C.c_int32 * METRICS_MAX_PLANES),
+                ("edt_plane", C.c_int32 * METRICS_MAX_PLANES),
+                ("out_offset", C.c_int64 * METRICS_MAX_PLANES), ("out_count", C.c_int64 * METRICS_MAX_PLANES), ("out_capacity", C.c_int64),
+                ("borders", C.c_void_p), ("edt", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 def header_abi_version() -> int:
@@ -392,6 +419,11 @@ class SegmLib:
         sig("segm_selective_scan_regular_shape", [C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_int32], C.c_int32)
         sig("segm_channel_sum", [C.POINTER(ChannelSumArgs)], C.c_int)
         sig("segm_channel_sum_workspace_bytes", [C.c_int32, C.c_int32, C.c_int64], C.c_size_t)
+        sig("segm_seg_regions", [C.POINTER(SegRegionsArgs)], C.c_int)
+        sig("segm_seg_regions_workspace_bytes", [C.c_int64], C.c_size_t)
+        sig("segm_edt_sq", [C.POINTER(EdtSqArgs)], C.c_int)
+        sig("segm_border_distances", [C.POINTER(BorderDistancesArgs)], C.c_int)
+        sig("segm_border_distances_workspace_bytes", [C.c_int64, C.c_int32], C.c_size_t)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

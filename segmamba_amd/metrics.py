@@ -1,0 +1,231 @@
+"""Evaluation on the device: Dice, Hausdorff distance and HD95 of label volumes (csrc/metrics.hip).
+
+The last stage of the reference's pipeline, `5_compute_metrics.py`, calls `medpy.metric.binary.dc / hd95` per BraTS region on
+the host; `3_train.py:82-119` computes a validation Dice the same way.  The functions here carry medpy's names and definitions
+(connectivity 1, `numpy.percentile` interpolation) and run on the library's kernels: one pass for region counts and borders, one
+batched exact squared distance transform, one gather of the distances at the border voxels.  Tensors stay on the device; numpy
+arrays and host tensors are uploaded.  Only a handful of scalars is read back per call.
+"""
+from __future__ import annotations
+
+import math
+from typing import Iterable, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import lib as L
+from . import ops_raw
+
+BRATS_REGIONS: Tuple[Tuple[int, ...], ...] = ((1, 3), (1, 2, 3), (3,))      # TC, WT, ET (5_compute_metrics.py:40-46)
+_BINARY = ((1,),)
+_INT_SENTINEL = 2 ** 31 - 1
+
+_tables = {}
+
+
+def _table(regions, device) -> torch.Tensor:
+    """the 256-entry label -> region-bits table of `regions` on `device`"""
+    regions = tuple(tuple(int(v) for v in r) for r in regions)
+    if not 1 <= len(regions) <= L.METRICS_MAX_REGIONS:
+        raise RuntimeError(f"between 1 and {L.METRICS_MAX_REGIONS} regions per call, got {len(regions)}")
+    key = (regions, str(device))
+    if key not in _tables:
+        t = np.zeros(256, dtype=np.uint8)
+        for r, labels in enumerate(regions):
+            for v in labels:
+                if not 0 <= v <= 255:
+                    raise RuntimeError(f"label {v} of region {r} is outside [0, 255]")
+                t[v] |= 1 << r
+        _tables[key] = torch.from_numpy(t).to(device)
+    return _tables[key]
+
+
+def _to_device(x) -> torch.Tensor:
+    t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"a tensor or a numpy array is required, got {type(x)}")
+    if not L.on_device(t):
+        t = t.to("cuda")
+    return t
+
+
+def _labels(x) -> torch.Tensor:
+    """a label volume as the kernels take it: uint8, contiguous, on the device (labels must lie in [0, 255])"""
+    t = _to_device(x)
+    if t.dtype != torch.uint8:
+        t = t.to(torch.uint8)
+    return t.contiguous()
+
+
+def _mask(x) -> torch.Tensor:
+    """medpy's `astype(bool)`: non-zero = inside"""
+    t = _to_device(x)
+    return (t != 0).to(torch.uint8).contiguous()
+
+
+def _volume3(t: torch.Tensor, what: str) -> torch.Tensor:
+    if t.dim() != 3:
+        raise RuntimeError(f"{what}: a (D, H, W) volume is required, got shape {tuple(t.shape)}")
+    return t
+
+
+def _pair(result, reference, conv, what):
+    a, b = _volume3(conv(result), what), _volume3(conv(reference), what)
+    if a.shape != b.shape:
+        raise RuntimeError(f"{what}: shapes {tuple(a.shape)} and {tuple(b.shape)} differ")
+    if b.device != a.device:
+        b = b.to(a.device)
+    return a, b
+
+
+def _dice(p: int, g: int, both: int) -> float:
+    return 2.0 * both / float(p + g) if p + g > 0 else 0.0
+
+
+def region_masks(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS) -> torch.Tensor:
+    """`convert_labels` of the reference: (n_regions, *labels.shape) fp32 masks, region r = labels in regions[r]"""
+    t = _labels(labels)
+    bits = _table(regions, t.device)[t.long()]
+    return torch.stack([(bits >> r) & 1 for r in range(len(regions))]).float()
+
+
+def dc(result, reference) -> float:
+    """Dice coefficient 2 n(A and B) / (n(A) + n(B)) of two binary volumes; 0.0 when both are empty (medpy.metric.binary.dc)"""
+    a, b = _pair(result, reference, _mask, "dc")
+    _, counts = ops_raw.seg_regions(L.get_lib(), a, b, _table(_BINARY, a.device))
+    c = counts[:, 0].tolist()
+    return _dice(c[0], c[1], c[2])
+
+
+def distance_transform_edt(mask, sampling: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """scipy.ndimage.distance_transform_edt: the distance of every non-zero voxel to the nearest zero voxel (0 at zero voxels), fp32;
+    +inf everywhere when `mask` has no zero voxel.  Each side of the volume is limited to 256 voxels."""
+    m = _volume3(_to_device(mask), "distance_transform_edt")
+    zero = (m == 0).to(torch.uint8).contiguous()
+    e = ops_raw.edt_sq(L.get_lib(), zero[None], [(0, 0)], sampling)[0]
+    if e.dtype == torch.int32:
+        return torch.where(e == _INT_SENTINEL, torch.full((), math.inf, device=e.device), e.float().sqrt())
+    return e.sqrt()
+
+
+class _Pass:
+    """region counts and borders of one (prediction, ground truth) pair, and the border-to-border distance lists made from them"""
+
+    def __init__(self, pred: torch.Tensor, gt: torch.Tensor, regions):
+        self.lib = L.get_lib()
+        self.n_regions = len(regions)
+        self.borders, counts = ops_raw.seg_regions(self.lib, pred, gt, _table(regions, pred.device))
+        self.counts = counts[:, :self.n_regions].tolist()                 # first readback: [|P|, |G|, |P and G|, |dP|, |dG|][region]
+
+    def live(self, r: int) -> bool:
+        return self.counts[0][r] > 0 and self.counts[1][r] > 0
+
+    def dice(self, r: int) -> float:
+        return _dice(self.counts[0][r], self.counts[1][r], self.counts[2][r])
+
+    def distances(self, regions_idx, spacing):
+        """-> (flat fp32 vector, [(offset, n(border P), n(border G))] per region of `regions_idx`): for each region the distances from
+        the border of P to the border of G, then from the border of G to the border of P"""
+        planes, items, cnt, seg = [], [], [], []
+        off = 0
+        for i, r in enumerate(regions_idx):
+            planes += [(0, r), (1, r)]                                    # edt plane 2 i: to the border of P; 2 i + 1: to the border of G
+            items += [(0, r, 2 * i + 1), (1, r, 2 * i)]
+            n_p, n_g = self.counts[3][r], self.counts[4][r]
+            cnt += [n_p, n_g]
+            seg.append((off, n_p, n_g))
+            off += n_p + n_g
+        edt = ops_raw.edt_sq(self.lib, self.borders, planes, spacing)
+        return ops_raw.border_distances(self.lib, self.borders, edt, items, cnt), seg
+
+    def hausdorff(self, regions_idx, spacing):
+        """-> [(hd95, hd)] per region of `regions_idx`, with one readback for all of them"""
+        if not regions_idx:
+            return []
+        dist, seg = self.distances(regions_idx, spacing)
+        picks, frac = [], []
+        for off, n_p, n_g in seg:
+            n = n_p + n_g
+            s = torch.sort(dist[off:off + n]).values
+            rank = 0.95 * (n - 1)                                         # numpy.percentile, linear interpolation
+            lo = int(math.floor(rank))
+            hi = min(lo + 1, n - 1)
+            frac.append(rank - lo)
+            picks.append(s[[lo, hi, n - 1]])
+        vals = torch.stack(picks).double().cpu().numpy()                  # second readback
+        return [(float(v[0] + (v[1] - v[0]) * f), float(v[2])) for v, f in zip(vals, frac)]
+
+
+def _binary_pass(result, reference, what) -> _Pass:
+    a, b = _pair(result, reference, _mask, what)
+    p = _Pass(a, b, _BINARY)
+    if p.counts[0][0] == 0:
+        raise RuntimeError("The first supplied array does not contain any binary object.")
+    if p.counts[1][0] == 0:
+        raise RuntimeError("The second supplied array does not contain any binary object.")
+    return p
+
+
+def surface_distances(result, reference, voxelspacing: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """medpy's `__surface_distances` (connectivity 1): the distance from every border voxel of `result` (in memory order) to the nearest
+    border voxel of `reference`, fp32 on the device.  Raises RuntimeError when either volume is empty, as medpy does."""
+    p = _binary_pass(result, reference, "surface_distances")
+    dist, seg = p.distances([0], voxelspacing)
+    return dist[:seg[0][1]]
+
+
+def hd95(result, reference, voxelspacing: Optional[Sequence[float]] = None) -> float:
+    """95th percentile of the joined surface distances result -> reference and reference -> result (medpy.metric.binary.hd95:
+    `numpy.percentile(hstack(...), 95)`, linear interpolation)"""
+    return _binary_pass(result, reference, "hd95").hausdorff([0], voxelspacing)[0][0]
+
+
+def hd(result, reference, voxelspacing: Optional[Sequence[float]] = None) -> float:
+    """Hausdorff distance: the maximum of the same joined list (medpy.metric.binary.hd)"""
+    return _binary_pass(result, reference, "hd").hausdorff([0], voxelspacing)[0][1]
+
+
+def case_metrics(pred_labels, gt_labels, voxelspacing: Optional[Sequence[float]] = (1, 1, 1),
+                 regions: Sequence[Sequence[int]] = BRATS_REGIONS) -> np.ndarray:
+    """`each_cases_metric` of 5_compute_metrics.py on label volumes: (n_regions, 2) = [dice, hd95] per region, with the reference's rule
+    for empty masks (`cal_metric`, :24-30): [0.0, 50] unless both the prediction and the ground truth of the region are non-empty."""
+    pred, gt = _pair(pred_labels, gt_labels, _labels, "case_metrics")
+    p = _Pass(pred, gt, regions)
+    out = np.zeros((len(regions), 2), dtype=np.float64)
+    out[:, 1] = 50.0
+    live = [r for r in range(len(regions)) if p.live(r)]
+    for r, (h95, _) in zip(live, p.hausdorff(live, voxelspacing)):
+        out[r] = (p.dice(r), h95)
+    return out
+
+
+def validation_dice(pred_labels, gt_labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS) -> np.ndarray:
+    """The validation rule of 3_train.py:82-119 per region: Dice if both are non-empty, 1.0 if both are empty, else 0.0.  Counts only;
+    leading batch dimensions are counted as one volume, as the reference does."""
+    pred, gt = _labels(pred_labels), _labels(gt_labels)
+    if pred.shape != gt.shape or pred.dim() < 3:
+        raise RuntimeError(f"validation_dice: two label tensors of one shape (..., D, H, W) are required, got {tuple(pred.shape)} and {tuple(gt.shape)}")
+    if gt.device != pred.device:
+        gt = gt.to(pred.device)
+    shape = (-1,) + tuple(pred.shape[-2:])
+    _, counts = ops_raw.seg_regions(L.get_lib(), pred.reshape(shape), gt.reshape(shape), _table(regions, pred.device))
+    c = counts[:, :len(regions)].tolist()
+    out = np.zeros(len(regions), dtype=np.float64)
+    for r in range(len(regions)):
+        n_p, n_g, both = c[0][r], c[1][r], c[2][r]
+        out[r] = _dice(n_p, n_g, both) if n_p > 0 and n_g > 0 else (1.0 if n_p == 0 and n_g == 0 else 0.0)
+    return out
+
+
+def evaluate(cases: Iterable, regions: Sequence[Sequence[int]] = BRATS_REGIONS):
+    """cases: an iterable of (pred_labels, gt_labels) or (pred_labels, gt_labels, voxelspacing).  -> (results (n, n_regions, 2), their
+    mean over the cases, their standard deviation): what 5_compute_metrics.py:76-84 saves and prints."""
+    rows = []
+    for case in cases:
+        spacing = case[2] if len(case) > 2 else (1, 1, 1)
+        rows.append(case_metrics(case[0], case[1], spacing, regions))
+    results = np.stack(rows) if rows else np.zeros((0, len(regions), 2))
+    if not rows:
+        return results, np.full((len(regions), 2), np.nan), np.full((len(regions), 2), np.nan)
+    return results, results.mean(axis=0), results.std(axis=0)

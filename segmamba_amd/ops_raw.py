@@ -1383,6 +1383,126 @@ def wgrad_gemm(lib: L.SegmLib, a: torch.Tensor, b: torch.Tensor, layout: int) ->
 
 
 # ---------------------------------------------------------------------------------------------------------
+# evaluation (csrc/metrics.hip): region counts and borders, squared distance transform, border distances
+# ---------------------------------------------------------------------------------------------------------
+def _label_volume(t: torch.Tensor, what: str, dims=(3,)) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise RuntimeError(f"{what}: a uint8 tensor is required, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() not in dims:
+        raise RuntimeError(f"{what}: {' or '.join(str(d) for d in dims)} dimensions required, got shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{what}: must be contiguous")
+    if t.numel() == 0 or t.numel() > L.METRICS_MAX_VOXELS * (t.shape[0] if t.dim() == 4 else 1):
+        raise RuntimeError(f"{what}: between 1 and {L.METRICS_MAX_VOXELS} voxels per volume, got shape {tuple(t.shape)}")
+
+
+def seg_regions(lib: L.SegmLib, pred: torch.Tensor, gt: torch.Tensor, table: torch.Tensor):
+    """pred, gt (D, H, W) uint8 label volumes; table (256,) uint8, bit r of table[l] = label l belongs to region r.
+    -> (borders, counts): borders (2, D, H, W) uint8, the border bits of pred [0] and gt [1] (bit r = region r); counts (5, 8) int64 =
+    |P|, |G|, |P and G|, |border P|, |border G| per region (still on the device)."""
+    _label_volume(pred, "seg_regions: pred")
+    _label_volume(gt, "seg_regions: gt")
+    if pred.shape != gt.shape:
+        raise RuntimeError(f"seg_regions: pred {tuple(pred.shape)} and gt {tuple(gt.shape)} differ in shape")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or tuple(table.shape) != (256,) or not table.is_contiguous():
+        raise RuntimeError("seg_regions: table must be a contiguous uint8 tensor of 256 entries")
+    if gt.device != pred.device or table.device != pred.device:
+        raise RuntimeError("seg_regions: pred, gt and table must be on one device")
+    D, H, W = pred.shape
+    borders = torch.empty(2, D, H, W, dtype=torch.uint8, device=pred.device)
+    counts = torch.empty(5, L.METRICS_MAX_REGIONS, dtype=torch.int64, device=pred.device)
+    nbytes = lib.dll.segm_seg_regions_workspace_bytes(pred.numel())
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=pred.device)
+    a = L.SegRegionsArgs()
+    a.depth, a.height, a.width = D, H, W
+    a.pred, a.gt, a.table, a.border_pred, a.border_gt = pred.data_ptr(), gt.data_ptr(), table.data_ptr(), borders[0].data_ptr(), borders[1].data_ptr()
+    a.counts, a.workspace, a.workspace_bytes, a.stream = counts.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(pred)
+    lib.check(lib.dll.segm_seg_regions(a), "seg_regions")
+    return borders, counts
+
+
+def _unit_spacing(spacing) -> bool:
+    return spacing is None or all(float(s) == 1.0 for s in spacing)
+
+
+def _spacing3(spacing):
+    if spacing is None:
+        return (1.0, 1.0, 1.0)
+    sp = tuple(float(s) for s in spacing)
+    if len(sp) != 3 or not all(0.0 < s < 1e15 for s in sp):
+        raise RuntimeError(f"spacing must be three positive numbers (z, y, x), got {spacing}")
+    return sp
+
+
+def _plane_list(planes, n_volumes: int, what: str):
+    planes = [(int(v), int(b)) for v, b in planes]
+    if not 1 <= len(planes) <= L.METRICS_MAX_PLANES:
+        raise RuntimeError(f"{what}: between 1 and {L.METRICS_MAX_PLANES} planes per call, got {len(planes)}")
+    for v, b in planes:
+        if not (0 <= v < n_volumes and 0 <= b < 8):
+            raise RuntimeError(f"{what}: plane (volume {v}, bit {b}) outside {n_volumes} volumes of 8 bits")
+    return planes
+
+
+def edt_sq(lib: L.SegmLib, volumes: torch.Tensor, planes, spacing=None) -> torch.Tensor:
+    """Squared Euclidean distance of every voxel to the nearest voxel whose bit is set, for a batch of bit planes.
+    volumes (V, D, H, W) uint8; planes: (volume, bit) pairs; spacing (z, y, x) or None.  -> (len(planes), D, H, W), int32 for unit
+    spacing (INT32_MAX where a plane has no set bit), fp32 otherwise (+inf)."""
+    _label_volume(volumes, "edt_sq: volumes", dims=(4,))
+    V, D, H, W = volumes.shape
+    if max(D, H, W) > L.EDT_MAX_LINE:
+        raise RuntimeError(f"edt_sq: depth, height and width are limited to {L.EDT_MAX_LINE} (SEGM_E_SHAPE), got {(D, H, W)}")
+    if V > L.METRICS_MAX_PLANES:
+        raise RuntimeError(f"edt_sq: at most {L.METRICS_MAX_PLANES} volumes per call, got {V}")
+    planes = _plane_list(planes, V, "edt_sq")
+    sp = _spacing3(spacing)
+    unit = _unit_spacing(spacing)
+    out = torch.empty(len(planes), D, H, W, dtype=torch.int32 if unit else torch.float32, device=volumes.device)
+    a = L.EdtSqArgs()
+    a.depth, a.height, a.width, a.n_volumes, a.n_planes, a.fp32 = D, H, W, V, len(planes), 0 if unit else 1
+    a.spacing_z, a.spacing_y, a.spacing_x = sp
+    for i, (v, b) in enumerate(planes):
+        a.plane_volume[i], a.plane_bit[i] = v, b
+    a.volumes, a.out, a.stream = volumes.data_ptr(), out.data_ptr(), L.stream_handle(volumes)
+    lib.check(lib.dll.segm_edt_sq(a), "edt_sq")
+    return out
+
+
+def border_distances(lib: L.SegmLib, borders: torch.Tensor, edt: torch.Tensor, items, counts) -> torch.Tensor:
+    """borders (V, D, H, W) uint8 bit planes; edt (P, D, H, W) int32 / fp32 squared distances; items: (volume, bit, edt plane)
+    triples; counts: the number of set voxels of each item's border (as seg_regions counted them).  -> one fp32 vector: the
+    items' distance lists sqrt(edt[plane][v]) over their border voxels v in memory order, one after the other."""
+    _label_volume(borders, "border_distances: borders", dims=(4,))
+    if not isinstance(edt, torch.Tensor) or edt.dtype not in (torch.int32, torch.float32) or edt.dim() != 4 or not edt.is_contiguous():
+        raise RuntimeError("border_distances: edt must be a contiguous (P, D, H, W) int32 or fp32 tensor")
+    if edt.shape[1:] != borders.shape[1:] or edt.device != borders.device:
+        raise RuntimeError(f"border_distances: borders {tuple(borders.shape)} and edt {tuple(edt.shape)} must share volume shape and device")
+    items = [(int(v), int(b), int(p)) for v, b, p in items]
+    _plane_list([(v, b) for v, b, _ in items], borders.shape[0], "border_distances")
+    counts = [int(c) for c in counts]
+    if len(counts) != len(items) or any(c < 0 for c in counts) or any(not 0 <= p < edt.shape[0] for _, _, p in items):
+        raise RuntimeError("border_distances: one non-negative count per item and edt planes inside `edt` are required")
+    N = borders[0].numel()
+    total = sum(counts)
+    out = torch.empty(total, dtype=torch.float32, device=borders.device)
+    if total == 0:
+        return out
+    nbytes = lib.dll.segm_border_distances_workspace_bytes(N, len(items))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=borders.device)
+    a = L.BorderDistancesArgs()
+    a.voxels, a.n_volumes, a.n_planes, a.n_items, a.fp32 = N, borders.shape[0], edt.shape[0], len(items), int(edt.dtype == torch.float32)
+    off = 0
+    for i, ((v, b, p), c) in enumerate(zip(items, counts)):
+        a.border_volume[i], a.border_bit[i], a.edt_plane[i], a.out_offset[i], a.out_count[i] = v, b, p, off, c
+        off += c
+    a.out_capacity = total
+    a.borders, a.edt, a.out = borders.data_ptr(), edt.data_ptr(), out.data_ptr()
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), nbytes, L.stream_handle(borders)
+    lib.check(lib.dll.segm_border_distances(a), "border_distances")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -1425,5 +1545,5 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "instnorm_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
-              "space_to_depth2"):
+              "space_to_depth2", "seg_regions", "edt_sq", "border_distances"):
     globals()[_name] = _device_guard(globals()[_name])

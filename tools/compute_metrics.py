@@ -1,0 +1,79 @@
+"""Dice and HD95 per BraTS region (TC / WT / ET) of predicted label volumes against ground truth, on the device: the command-line
+form of the reference's 5_compute_metrics.py.
+
+    python tools/compute_metrics.py --pred DIR --gt DIR [--out FILE.npy] [--spacing Z Y X]
+
+Cases are the files of --pred that have a file of the same name in --gt.  Label volumes are read from .npy and .npz (the first
+array, or the one called "labels" / "seg" / "arr_0"); .nii / .nii.gz only where nibabel or SimpleITK is installed.  Prints the
+per-case array, then its mean and standard deviation over the cases, and saves the (cases, regions, 2) array to --out."""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np          # noqa: E402
+
+EXTS = (".npy", ".npz", ".nii.gz", ".nii")
+
+
+def load_labels(path: str) -> np.ndarray:
+    if path.endswith(".npy"):
+        a = np.load(path)
+    elif path.endswith(".npz"):
+        with np.load(path) as z:
+            name = next((k for k in ("labels", "seg", "arr_0") if k in z.files), z.files[0])
+            a = z[name]
+    else:
+        try:
+            import nibabel
+            a = np.asarray(nibabel.load(path).dataobj).transpose(2, 1, 0)          # (x, y, z) on disk -> (z, y, x)
+        except ImportError:
+            try:
+                import SimpleITK as sitk
+                a = sitk.GetArrayFromImage(sitk.ReadImage(path))
+            except ImportError:
+                raise RuntimeError(f"{path}: reading NIfTI needs nibabel or SimpleITK; convert the volume to .npy instead") from None
+    a = np.squeeze(np.asarray(a))
+    if a.ndim != 3:
+        raise RuntimeError(f"{path}: a 3-D label volume is required, got shape {a.shape}")
+    if a.min() < 0 or a.max() > 255:
+        raise RuntimeError(f"{path}: labels must lie in [0, 255]")
+    return np.ascontiguousarray(a.astype(np.uint8))
+
+
+def case_files(pred_dir: str, gt_dir: str):
+    names = sorted(n for n in os.listdir(pred_dir) if n.endswith(EXTS) and os.path.exists(os.path.join(gt_dir, n)))
+    if not names:
+        raise RuntimeError(f"no file of {pred_dir} ({', '.join(EXTS)}) has a file of the same name in {gt_dir}")
+    return names
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--pred", required=True)
+    ap.add_argument("--gt", required=True)
+    ap.add_argument("--out")
+    ap.add_argument("--spacing", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("Z", "Y", "X"))
+    args = ap.parse_args(argv)
+    from segmamba_amd import metrics
+    names = case_files(args.pred, args.gt)
+
+    def cases():
+        for n in names:
+            yield load_labels(os.path.join(args.pred, n)), load_labels(os.path.join(args.gt, n)), tuple(args.spacing)
+    results, mean, std = metrics.evaluate(cases())
+    for n, r in zip(names, results):
+        print(n, r.tolist())
+    print(results.shape)
+    print(mean)
+    print(std)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        np.save(args.out, results)
+    return results
+
+
+if __name__ == "__main__":
+    main()
