@@ -883,6 +883,89 @@ typedef struct segm_border_distances_args {
 size_t segm_border_distances_workspace_bytes(int64_t voxels, int32_t n_items);
 int segm_border_distances(const segm_border_distances_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * Finishing a prediction on the device (additive to ABI 10; csrc/postprocess.hip).
+ * Replaces, of the reference's light_training/prediction.py: predict_raw_probability (:33-62) + the argmax of 4_predict.py:81 +
+ * predict_noncrop_probability (:64-108) by ONE launch, and large_connected_domain (:17-27: skimage.measure.label at connectivity 1,
+ * keep the largest, scipy.ndimage.binary_fill_holes) by connected components on the device.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_RESAMPLE_MAX_CLASSES 8
+#define SEGM_CCL_MAX_VOXELS 2147483647LL         /* depth * height * width < 2^31: labels are int32 linear indices */
+
+/* Logits (classes, in_depth, in_height, in_width) -> uint8 label volume (out_depth, out_height, out_width).  For every voxel of the
+ * box [box_z, box_z + box_depth) x [box_y, ..) x [box_x, ..) the trilinear sample of each class at the voxel's source coordinate
+ * (F.interpolate(mode="trilinear", align_corners=False) from the logits' size to the box's size: per axis
+ * src = max((dst + 0.5) * (in / out) - 0.5, 0), i0 = floor(src), i1 = min(i0 + 1, in - 1), lambda = src - i0, fp32 arithmetic), the index
+ * of the largest (the first of equal values), one byte; every voxel outside the box is written 0 by the same launch.  When the box has
+ * the logits' size the weights are exactly 0 / 1 and the result is the plain argmax.
+ * regions (optional, else NULL): a second (out_depth, out_height, out_width) uint8 volume = table[label], the region bit planes that
+ * the evaluation entries take; `table` (256 bytes, device memory) is required with it.
+ * dtype SEGM_F32 / SEGM_F16 / SEGM_BF16; element strides for class, z and y, unit stride along x; `logits` aligned to its element size. */
+typedef struct segm_resample_argmax_args {
+    int32_t classes, dtype;
+    int32_t in_depth, in_height, in_width;
+    int32_t box_z, box_y, box_x;
+    int32_t box_depth, box_height, box_width;
+    int32_t out_depth, out_height, out_width;
+    int64_t stride_c, stride_z, stride_y;
+    const void* logits;
+    uint8_t* labels;
+    uint8_t* regions;              /* optional */
+    const uint8_t* table;          /* required with regions */
+    void* stream;
+} segm_resample_argmax_args;
+int segm_resample_argmax(const segm_resample_argmax_args* args);
+
+/* Connected components at connectivity 1 (six face neighbours; the outside of the volume connects nothing).
+ * A voxel is inside the mask iff ((bit >= 0 ? (v >> bit) & 1 : v != 0) != invert), v its byte of `volume`.
+ *   roots[i] = -1 outside the mask, otherwise the SMALLEST linear index (z * height + y) * width + x of the voxel's component
+ * - a definition that does not depend on the order in which anything happened: two calls are bit-equal.
+ * Three launches, no readback, whatever the volume: labels of 64 x 4 x 4 tiles converge in LDS, tile faces are joined by a
+ * lock-free union-find on agent-scope atomic min (workspace: one int32 per voxel), a last pass replaces every label by its root. */
+typedef struct segm_ccl_roots_args {
+    int32_t depth, height, width;
+    int32_t bit;                   /* 0 .. 7, or -1: value != 0 */
+    int32_t invert, reserved;
+    const uint8_t* volume;
+    int32_t* roots;                /* (depth, height, width) */
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_ccl_roots_args;
+size_t segm_ccl_roots_workspace_bytes(int64_t voxels);
+int segm_ccl_roots(const segm_ccl_roots_args* args);
+
+/* From the roots: sizes[i] = the voxel count of the component whose root is voxel i, 0 at every other voxel (integer atomics:
+ * exact); touches[i] = 1 at a root whose component has a voxel on a face of the volume, 0 elsewhere.  Both are OVERWRITTEN. */
+typedef struct segm_ccl_sizes_args {
+    int32_t depth, height, width, reserved;
+    const int32_t* roots;
+    int32_t* sizes;                /* (depth, height, width) */
+    uint8_t* touches;              /* (depth, height, width) */
+    void* stream;
+} segm_ccl_sizes_args;
+int segm_ccl_sizes(const segm_ccl_sizes_args* args);
+
+enum segm_ccl_select_mode {
+    SEGM_CCL_LARGEST = 0,          /* the component with the most voxels; of equally large ones the one whose root comes LAST in memory */
+    SEGM_CCL_MIN_SIZE = 1,         /* every component of at least min_size voxels */
+    SEGM_CCL_FILL = 2              /* roots of the INVERTED mask: out = mask | (zero voxels whose zero-component touches no face) */
+};
+/* out (uint8 0 / 1) by `mode`.  info (3 int64 in device memory, OVERWRITTEN): the number of components, the root of the largest
+ * (-1 when there is none) and its voxel count - a device reduction over the root counts (per-workgroup partials in the workspace). */
+typedef struct segm_ccl_select_args {
+    int32_t depth, height, width;
+    int32_t mode, min_size, reserved;
+    const int32_t* roots;
+    const int32_t* sizes;
+    const uint8_t* touches;        /* SEGM_CCL_FILL only, else may be NULL */
+    uint8_t* out;                  /* (depth, height, width) */
+    int64_t* info;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_ccl_select_args;
+size_t segm_ccl_select_workspace_bytes(int64_t voxels);
+int segm_ccl_select(const segm_ccl_select_args* args);
+
 
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);

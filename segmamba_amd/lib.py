@@ -297,6 +297,8 @@ EXPORTS = (
     "segm_stem_conv_wgrad", "segm_stem_conv_wgrad_workspace_bytes", "segm_stem_conv_wgrad_workspace_bytes2", "segm_wgrad_gemm", "segm_wgrad_gemm_workspace_bytes",
     "segm_skinny_tn", "segm_skinny_tn_workspace_bytes", "segm_channel_sum", "segm_channel_sum_workspace_bytes", "segm_selective_scan_regular_shape",
     "segm_seg_regions", "segm_seg_regions_workspace_bytes", "segm_edt_sq", "segm_border_distances", "segm_border_distances_workspace_bytes",
+    "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
+    "segm_ccl_select_workspace_bytes",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -336,6 +338,39 @@ class BorderDistancesArgs(C.Structure):
                 ("edt_plane", C.c_int32 * METRICS_MAX_PLANES),
                 ("out_offset", C.c_int64 * METRICS_MAX_PLANES), ("out_count", C.c_int64 * METRICS_MAX_PLANES), ("out_capacity", C.c_int64),
                 ("borders", C.c_void_p), ("edt", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+RESAMPLE_MAX_CLASSES, CCL_MAX_VOXELS = 8, 2 ** 31 - 1                         # SEGM_RESAMPLE_MAX_CLASSES / SEGM_CCL_MAX_VOXELS
+CCL_LARGEST, CCL_MIN_SIZE, CCL_FILL = 0, 1, 2                                  # enum segm_ccl_select_mode
+
+
+class ResampleArgmaxArgs(C.Structure):
+    _fields_ = [("classes", C.c_int32), ("dtype", C.c_int32),
+                ("in_depth", C.c_int32), ("in_height", C.c_int32), ("in_width", C.c_int32),
+                ("box_z", C.c_int32), ("box_y", C.c_int32), ("box_x", C.c_int32),
+                ("box_depth", C.c_int32), ("box_height", C.c_int32), ("box_width", C.c_int32),
+                ("out_depth", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
+                ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("logits", C.c_void_p), ("labels", C.c_void_p), ("regions", C.c_void_p), ("table", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class CclRootsArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("bit", C.c_int32),
+                ("invert", C.c_int32), ("reserved", C.c_int32),
+                ("volume", C.c_void_p), ("roots", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class CclSizesArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("roots", C.c_void_p), ("sizes", C.c_void_p), ("touches", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class CclSelectArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("mode", C.c_int32), ("min_size", C.c_int32), ("reserved", C.c_int32),
+                ("roots", C.c_void_p), ("sizes", C.c_void_p), ("touches", C.c_void_p), ("out", C.c_void_p), ("info", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
@@ -424,6 +459,12 @@ class SegmLib:
         sig("segm_edt_sq", [C.POINTER(EdtSqArgs)], C.c_int)
         sig("segm_border_distances", [C.POINTER(BorderDistancesArgs)], C.c_int)
         sig("segm_border_distances_workspace_bytes", [C.c_int64, C.c_int32], C.c_size_t)
+        sig("segm_resample_argmax", [C.POINTER(ResampleArgmaxArgs)], C.c_int)
+        sig("segm_ccl_roots", [C.POINTER(CclRootsArgs)], C.c_int)
+        sig("segm_ccl_roots_workspace_bytes", [C.c_int64], C.c_size_t)
+        sig("segm_ccl_sizes", [C.POINTER(CclSizesArgs)], C.c_int)
+        sig("segm_ccl_select", [C.POINTER(CclSelectArgs)], C.c_int)
+        sig("segm_ccl_select_workspace_bytes", [C.c_int64], C.c_size_t)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

@@ -1503,6 +1503,144 @@ def border_distances(lib: L.SegmLib, borders: torch.Tensor, edt: torch.Tensor, i
 
 
 # ---------------------------------------------------------------------------------------------------------
+# finishing a prediction (csrc/postprocess.hip): logits -> labels, connected components, sizes, selection
+# ---------------------------------------------------------------------------------------------------------
+def _same_volume(t, what: str, dtype, shape, device) -> None:
+    """a caller's buffer: dtype, shape, device and contiguity before its pointer leaves Python"""
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise RuntimeError(f"{what}: a {dtype} tensor is required, got {getattr(t, 'dtype', type(t))}")
+    if tuple(t.shape) != tuple(shape) or t.device != device or not t.is_contiguous():
+        raise RuntimeError(f"{what}: must be contiguous, of shape {tuple(shape)} and on {device}; got {tuple(t.shape)} on {t.device}")
+
+
+def _ccl_volume(t: torch.Tensor, what: str, dtype=torch.uint8) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise RuntimeError(f"{what}: a {dtype} tensor is required, got {getattr(t, 'dtype', type(t))}")
+    if t.dim() != 3:
+        raise RuntimeError(f"{what}: a (D, H, W) volume is required, got shape {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{what}: must be contiguous")
+    if t.numel() == 0 or t.numel() > L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"{what}: between 1 and 2^31 - 1 voxels, got shape {tuple(t.shape)}")
+
+
+def resample_argmax(lib: L.SegmLib, logits: torch.Tensor, out_shape=None, box_start=(0, 0, 0), box_shape=None, table=None,
+                    out: torch.Tensor = None):
+    """logits (C, d, h, w) fp32 / bf16 / fp16 with a unit stride along w, C <= 8.  -> uint8 labels of shape `out_shape`: inside the box
+    `box_start` + `box_shape` the arg-max over the classes of the logits resampled (trilinear, align_corners False) to the box's
+    shape, 0 outside.  Defaults: the box has the logits' shape and fills the output.  With `table` (256 uint8, device) also the
+    region bit planes table[label]: -> (labels, regions)."""
+    if not isinstance(logits, torch.Tensor) or logits.dim() != 4:
+        raise RuntimeError(f"resample_argmax: logits (C, d, h, w) required, got {getattr(logits, 'shape', type(logits))}")
+    dtype = L.dtype_code(logits)
+    C_, d, h, w = logits.shape
+    if not 1 <= C_ <= L.RESAMPLE_MAX_CLASSES or min(d, h, w) < 1:
+        raise RuntimeError(f"resample_argmax: 1 .. {L.RESAMPLE_MAX_CLASSES} classes and a non-empty volume, got {tuple(logits.shape)}")
+    sc, sz, sy, sx = logits.stride()
+    if w > 1 and sx != 1:
+        raise RuntimeError("resample_argmax: logits need a unit stride along the last dimension")
+    if (h > 1 and sy < w) or min(sc, sz) < 0:
+        raise RuntimeError(f"resample_argmax: unsupported logits strides {logits.stride()}")
+    box_shape = (d, h, w) if box_shape is None else tuple(int(v) for v in box_shape)
+    box_start = tuple(int(v) for v in box_start)
+    out_shape = tuple(b0 + bs for b0, bs in zip(box_start, box_shape)) if out_shape is None else tuple(int(v) for v in out_shape)
+    if len(box_shape) != 3 or len(box_start) != 3 or len(out_shape) != 3:
+        raise RuntimeError("resample_argmax: out_shape, box_start and box_shape have three entries each")
+    if any(bs < 1 or b0 < 0 or b0 + bs > o for b0, bs, o in zip(box_start, box_shape, out_shape)):
+        raise RuntimeError(f"resample_argmax: the box {box_start} + {box_shape} does not lie inside the output {out_shape}")
+    n = out_shape[0] * out_shape[1] * out_shape[2]
+    if n > L.CCL_MAX_VOXELS or max(d, h, w, *out_shape) > L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"resample_argmax: at most 2^31 - 1 output voxels, got {out_shape}")
+    if out is None:
+        out = torch.empty(out_shape, dtype=torch.uint8, device=logits.device)
+    else:
+        _same_volume(out, "resample_argmax: out", torch.uint8, out_shape, logits.device)
+    regions = None
+    if table is not None:
+        if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or tuple(table.shape) != (256,) or not table.is_contiguous() \
+                or table.device != logits.device:
+            raise RuntimeError("resample_argmax: table must be a contiguous uint8 tensor of 256 entries on the logits' device")
+        regions = torch.empty(out_shape, dtype=torch.uint8, device=logits.device)
+    a = L.ResampleArgmaxArgs()
+    a.classes, a.dtype = C_, dtype
+    a.in_depth, a.in_height, a.in_width = d, h, w
+    a.box_z, a.box_y, a.box_x = box_start
+    a.box_depth, a.box_height, a.box_width = box_shape
+    a.out_depth, a.out_height, a.out_width = out_shape
+    a.stride_c, a.stride_z, a.stride_y = sc, sz, max(sy, w)
+    a.logits, a.labels, a.stream = logits.data_ptr(), out.data_ptr(), L.stream_handle(logits)
+    if regions is not None:
+        a.regions, a.table = regions.data_ptr(), table.data_ptr()
+    lib.check(lib.dll.segm_resample_argmax(a), "resample_argmax")
+    return out if regions is None else (out, regions)
+
+
+def ccl_roots(lib: L.SegmLib, volume: torch.Tensor, bit: int = -1, invert: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """Connected components at connectivity 1 of the mask `(volume >> bit) & 1` (bit = -1: `volume != 0`), or of its complement with
+    `invert`.  volume (D, H, W) uint8.  -> int32 (D, H, W): -1 outside the mask, else the smallest linear index of the voxel's component."""
+    _ccl_volume(volume, "ccl_roots: volume")
+    bit = int(bit)
+    if not -1 <= bit <= 7:
+        raise RuntimeError(f"ccl_roots: bit must be -1 or 0 .. 7, got {bit}")
+    if out is None:
+        out = torch.empty(volume.shape, dtype=torch.int32, device=volume.device)
+    else:
+        _same_volume(out, "ccl_roots: out", torch.int32, volume.shape, volume.device)
+    nbytes = lib.dll.segm_ccl_roots_workspace_bytes(volume.numel())
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=volume.device)
+    a = L.CclRootsArgs()
+    a.depth, a.height, a.width = volume.shape
+    a.bit, a.invert = bit, 1 if invert else 0
+    a.volume, a.roots, a.workspace, a.workspace_bytes, a.stream = volume.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(volume)
+    lib.check(lib.dll.segm_ccl_roots(a), "ccl_roots")
+    return out
+
+
+def ccl_sizes(lib: L.SegmLib, roots: torch.Tensor):
+    """roots as `ccl_roots` gives them.  -> (sizes int32 (D, H, W): the component's voxel count at its root voxel, 0 elsewhere;
+    touches uint8 (D, H, W): 1 at the roots whose component has a voxel on a face of the volume)."""
+    _ccl_volume(roots, "ccl_sizes: roots", torch.int32)
+    sizes = torch.empty(roots.shape, dtype=torch.int32, device=roots.device)
+    touches = torch.empty(roots.shape, dtype=torch.uint8, device=roots.device)
+    a = L.CclSizesArgs()
+    a.depth, a.height, a.width = roots.shape
+    a.roots, a.sizes, a.touches, a.stream = roots.data_ptr(), sizes.data_ptr(), touches.data_ptr(), L.stream_handle(roots)
+    lib.check(lib.dll.segm_ccl_sizes(a), "ccl_sizes")
+    return sizes, touches
+
+
+def ccl_select(lib: L.SegmLib, roots: torch.Tensor, sizes: torch.Tensor, mode: int, min_size: int = 0, touches: torch.Tensor = None,
+               out: torch.Tensor = None):
+    """-> (mask uint8 (D, H, W), info int64 (3,) on the device = [components, root of the largest or -1, its voxel count]).
+    mode L.CCL_LARGEST: the largest component (equal counts: the root that comes last); L.CCL_MIN_SIZE: every component of at least
+    `min_size` voxels; L.CCL_FILL (roots / sizes / touches of the INVERTED mask): the mask with its holes filled."""
+    _ccl_volume(roots, "ccl_select: roots", torch.int32)
+    _same_volume(sizes, "ccl_select: sizes", torch.int32, roots.shape, roots.device)
+    if mode not in (L.CCL_LARGEST, L.CCL_MIN_SIZE, L.CCL_FILL):
+        raise RuntimeError(f"ccl_select: unknown mode {mode}")
+    if mode == L.CCL_FILL or touches is not None:
+        _same_volume(touches, "ccl_select: touches", torch.uint8, roots.shape, roots.device)
+    min_size = int(min_size)
+    if not 0 <= min_size <= L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"ccl_select: min_size must lie in [0, 2^31 - 1], got {min_size}")
+    if out is None:
+        out = torch.empty(roots.shape, dtype=torch.uint8, device=roots.device)
+    else:
+        _same_volume(out, "ccl_select: out", torch.uint8, roots.shape, roots.device)
+    info = torch.empty(3, dtype=torch.int64, device=roots.device)
+    nbytes = lib.dll.segm_ccl_select_workspace_bytes(roots.numel())
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=roots.device)
+    a = L.CclSelectArgs()
+    a.depth, a.height, a.width = roots.shape
+    a.mode, a.min_size = mode, min_size
+    a.roots, a.sizes, a.out, a.info = roots.data_ptr(), sizes.data_ptr(), out.data_ptr(), info.data_ptr()
+    a.touches = None if touches is None else touches.data_ptr()
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), nbytes, L.stream_handle(roots)
+    lib.check(lib.dll.segm_ccl_select(a), "ccl_select")
+    return out, info
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -1545,5 +1683,5 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "instnorm_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
-              "space_to_depth2", "seg_regions", "edt_sq", "border_distances"):
+              "space_to_depth2", "seg_regions", "edt_sq", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select"):
     globals()[_name] = _device_guard(globals()[_name])

@@ -1,0 +1,145 @@
+"""Finishing a prediction on the device: logits -> label volume, connected components, hole filling (csrc/postprocess.hip).
+
+The stage of the reference's pipeline between `maybe_mirror_and_predict` and the file on disk (4_predict.py:75-99 on
+light_training/prediction.py): resample the logits to the pre-resample crop shape, arg-max, paste into the un-cropped volume
+(`labels_from_logits`: one launch), and the optional `large_connected_domain` post-processing - label the components, keep the
+largest, fill its holes (`largest_connected_domain`).  The functions carry the reference's, scipy's and skimage's names and
+definitions at connectivity 1 (six face neighbours; the only connectivity here), for 3-D volumes of fewer than 2^31 voxels.
+Tensors stay on the device; numpy arrays and host tensors are uploaded.  No call reads a volume back.
+
+Where this deliberately differs from the reference:
+  * `largest_connected_domain` of an empty mask returns the empty mask (the reference raises IndexError on `volume_sort[-1]`);
+  * of equally large components the one whose first voxel comes LAST in memory order is kept - a definition; the reference takes
+    `np.argsort(volume)[-1]`, which numpy leaves undefined for ties;
+  * the resampled logits are compared in fp32 (the CPU branch of `predict_raw_probability`; its GPU branch rounds them to fp16 first).
+`postprocess_labels` (per region of a label map) is this project's addition: the reference applies its function to one binary mask.
+"""
+from __future__ import annotations
+
+from typing import Optional, Sequence, Tuple
+
+import torch
+
+from . import lib as L
+from . import ops_raw
+from .metrics import BRATS_REGIONS, _table, _to_device
+
+
+def _mask(x, what: str) -> torch.Tensor:
+    """non-zero = inside: uint8, contiguous, (D, H, W), on the device"""
+    t = _to_device(x)
+    if t.dim() != 3:
+        raise RuntimeError(f"{what}: a (D, H, W) volume is required, got shape {tuple(t.shape)}")
+    if t.numel() == 0 or t.numel() > L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"{what}: between 1 and 2^31 - 1 voxels, got shape {tuple(t.shape)}")
+    if t.dtype != torch.uint8:
+        t = (t != 0).to(torch.uint8)
+    return t.contiguous()
+
+
+def component_roots(mask) -> torch.Tensor:
+    """int32 (D, H, W): -1 outside the mask, otherwise the smallest linear index of the voxel's component"""
+    return ops_raw.ccl_roots(L.get_lib(), _mask(mask, "component_roots"))
+
+
+def label(mask, return_num: bool = True):
+    """scipy.ndimage.label / skimage.measure.label(connectivity=1): int32 labels, 0 = background, the components numbered 1 .. num in
+    memory order of their first voxel.  -> (labels, num) or labels."""
+    roots = ops_raw.ccl_roots(L.get_lib(), _mask(mask, "label"))
+    flat = roots.reshape(-1)
+    is_root = flat == torch.arange(flat.numel(), dtype=torch.int32, device=flat.device)
+    rank = torch.cumsum(is_root, 0, dtype=torch.int32)                    # rank of a root among the roots = its number
+    labels = torch.where(flat >= 0, rank[flat.clamp(min=0).long()], torch.zeros((), dtype=torch.int32, device=flat.device))
+    labels = labels.reshape(roots.shape)
+    return (labels, int(rank[-1].item())) if return_num else labels
+
+
+def _fill(lib, m: torch.Tensor) -> torch.Tensor:
+    roots = ops_raw.ccl_roots(lib, m, invert=True)
+    sizes, touches = ops_raw.ccl_sizes(lib, roots)
+    return ops_raw.ccl_select(lib, roots, sizes, L.CCL_FILL, touches=touches)[0]
+
+
+def _keep(lib, m: torch.Tensor, keep, bit: int = -1) -> torch.Tensor:
+    roots = ops_raw.ccl_roots(lib, m, bit=bit)
+    sizes, _ = ops_raw.ccl_sizes(lib, roots)
+    if keep == "largest":
+        return ops_raw.ccl_select(lib, roots, sizes, L.CCL_LARGEST)[0]
+    return ops_raw.ccl_select(lib, roots, sizes, L.CCL_MIN_SIZE, min_size=int(keep))[0]
+
+
+def binary_fill_holes(mask) -> torch.Tensor:
+    """scipy.ndimage.binary_fill_holes with the default structure: the mask plus every zero voxel that no path of face-adjacent zero
+    voxels connects to a face of the volume.  -> uint8 0 / 1."""
+    return _fill(L.get_lib(), _mask(mask, "binary_fill_holes"))
+
+
+def remove_small_components(mask, min_size: int) -> torch.Tensor:
+    """the voxels of the components of at least `min_size` voxels (skimage.morphology.remove_small_objects keeps size >= min_size)"""
+    return _keep(L.get_lib(), _mask(mask, "remove_small_components"), int(min_size))
+
+
+def largest_connected_domain(mask) -> torch.Tensor:
+    """`large_connected_domain` of the reference (prediction.py:17-27): the largest component, its holes filled.  -> uint8 0 / 1.
+    An empty mask comes back empty; equal sizes: the component that comes last in memory order."""
+    lib = L.get_lib()
+    return _fill(lib, _keep(lib, _mask(mask, "largest_connected_domain"), "largest"))
+
+
+def component_summary(mask) -> Tuple[int, int]:
+    """(number of components, voxels of the largest): two scalars read back"""
+    lib = L.get_lib()
+    roots = ops_raw.ccl_roots(lib, _mask(mask, "component_summary"))
+    sizes, _ = ops_raw.ccl_sizes(lib, roots)
+    info = ops_raw.ccl_select(lib, roots, sizes, L.CCL_LARGEST)[1].tolist()
+    return int(info[0]), int(info[2])
+
+
+def _ints(v, n: int, what: str):
+    out = [int(x.item()) if isinstance(x, torch.Tensor) else int(x) for x in list(v)[:n]]
+    if len(out) != n:
+        raise RuntimeError(f"{what}: {n} entries required, got {v}")
+    return out
+
+
+def labels_from_logits(logits, properties: Optional[dict] = None, regions: Optional[Sequence[Sequence[int]]] = None):
+    """(C, d, h, w) or (1, C, d, h, w) logits -> uint8 label volume on the device, in one launch: `predict_raw_probability`, `argmax`
+    over the classes and `predict_noncrop_probability` of the reference.  With `properties` (the reference's loader's dict; ints or
+    0-d tensors) the logits are resampled to `shape_after_cropping_before_resample` and pasted at `bbox_used_for_cropping` into zeros of
+    `shape_before_cropping`; without it the labels have the logits' shape.  With `regions` also the region bit planes of the labels
+    (what `ops_raw.edt_sq` and the other evaluation kernels take): -> (labels, planes)."""
+    t = _to_device(logits)
+    if t.dim() == 5 and t.shape[0] == 1:
+        t = t[0]
+    if t.dim() != 4:
+        raise RuntimeError(f"labels_from_logits: (C, d, h, w) logits are required, got shape {tuple(t.shape)}")
+    if t.stride(-1) != 1 and t.shape[-1] > 1:
+        t = t.contiguous()
+    table = None if regions is None else _table(regions, t.device)
+    if properties is None:
+        return ops_raw.resample_argmax(L.get_lib(), t, table=table)
+    box_shape = _ints(properties["shape_after_cropping_before_resample"], 3, "shape_after_cropping_before_resample")
+    out_shape = _ints(properties["shape_before_cropping"], 3, "shape_before_cropping")
+    bbox = [_ints(bb, 2, "bbox_used_for_cropping") for bb in list(properties["bbox_used_for_cropping"])[:3]]
+    if len(bbox) != 3 or any(b1 - b0 != n for (b0, b1), n in zip(bbox, box_shape)):
+        raise RuntimeError(f"labels_from_logits: bbox_used_for_cropping {bbox} does not have the shape {box_shape}")
+    return ops_raw.resample_argmax(L.get_lib(), t, out_shape, [b0 for b0, _ in bbox], box_shape, table=table)
+
+
+def postprocess_labels(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS, keep="largest", fill_holes: bool = True) -> torch.Tensor:
+    """The per-region form for a label map (this project's addition).  For every region in turn: its mask is reduced to the kept
+    components (`keep` = "largest" or a minimum voxel count) and, with `fill_holes`, filled; the region's voxels that fall outside
+    the result become 0.  Voxels are only ever removed: a filled hole keeps whatever label it had.  -> uint8 labels."""
+    t = _to_device(labels)
+    if t.dim() != 3:
+        raise RuntimeError(f"postprocess_labels: a (D, H, W) label volume is required, got shape {tuple(t.shape)}")
+    out = (t if t.dtype == torch.uint8 else t.to(torch.uint8)).contiguous().clone()
+    lib = L.get_lib()
+    for r in range(len(regions)):
+        bits = _table(regions, out.device)[out.long()].contiguous()
+        kept = _keep(lib, bits, keep, bit=r)
+        if fill_holes:
+            kept = _fill(lib, kept)
+        inside = ((bits >> r) & 1).bool()
+        out[inside & (kept == 0)] = 0
+    return out

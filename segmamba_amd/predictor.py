@@ -2,8 +2,9 @@
 (SURVEY.md §8f rank 2).
 
 Host-side mirror of the reference's prediction path:
-  `Predictor`                light_training/prediction.py:29-159 (`maybe_mirror_and_predict`, `predict_raw_probability`,
-                             `predict_noncrop_probability`)
+  `Predictor`                light_training/prediction.py:29-227 (`maybe_mirror_and_predict`, `predict_raw_probability`,
+                             `predict_noncrop_probability`, `save_to_nii`; `predict_labels` = the middle two and the arg-max
+                             between them as one launch on the device, segmamba_amd/postprocess.py)
   `SlidingWindowInferer`     monai/inferers/inferer.py (the class 4_predict.py:55-59 and 3_train.py:35-37 construct), i.e.
   `sliding_window_inference` monai/inferers/utils.py:43-330 with its helpers `dense_patch_slices`
                              (monai/data/utils.py:171-211) and `compute_importance_map` (:1088-1138)
@@ -186,3 +187,43 @@ class Predictor:
         else:
             raise ValueError("restore crop error: expected a 3-D label map or a 4-D (C, ...) volume")
         return full
+
+    @staticmethod
+    def predict_labels(model_output, properties: Optional[dict] = None) -> torch.Tensor:
+        """`predict_raw_probability` -> `argmax` over the classes -> `predict_noncrop_probability` (4_predict.py:78-83) in one launch on
+        the device: the uint8 label volume of `shape_before_cropping` (segmamba_amd.postprocess.labels_from_logits).  The resampled
+        logits are compared in fp32, as the reference's CPU branch does."""
+        from . import postprocess
+        return postprocess.labels_from_logits(model_output, properties)
+
+    def save_to_nii(self, return_output, raw_spacing, save_dir, case_name, postprocess: bool = False) -> str:
+        """Write `<save_dir>/<case_name>.nii.gz` (reference :208-227).  `return_output`: a (D, H, W) label volume or mask, device tensor,
+        host tensor or numpy array; it is cast to uint8 as the reference does.  `postprocess` runs `largest_connected_domain` on the
+        device (an empty mask stays empty where the reference raises).  `raw_spacing` goes to the header unpermuted, as the
+        reference passes it to `SetSpacing`.
+        A (C, D, H, W) input is refused unless C == 1: SimpleITK would turn a 4-D array into a 3-D VECTOR image, which nothing
+        downstream of the reference reads as labels (4_predict.py passing its (3, ...) region stack is the reference's own loose end);
+        write one file per channel instead.  -> the path written."""
+        import os
+
+        from . import nifti
+        from . import postprocess as post
+        out = return_output
+        shape = tuple(out.shape)
+        if len(shape) == 4 and shape[0] == 1:
+            out = out[0]
+        elif len(shape) != 3:
+            raise RuntimeError(f"save_to_nii: a (D, H, W) volume (or (1, D, H, W)) is required, got shape {shape}; a (C, D, H, W) stack "
+                               "would become a vector image in the reference - write one file per channel")
+        if postprocess:
+            out = post.largest_connected_domain(out)                       # uploads numpy / host tensors, stays on the device
+        if isinstance(out, torch.Tensor):
+            out = out.to(torch.uint8).cpu().numpy()                        # the one copy to the host: one byte per voxel
+        else:
+            out = np.asarray(out).astype(np.uint8)
+        spacing = [float(v.item()) if isinstance(v, torch.Tensor) else float(v) for v in list(raw_spacing)[:3]]
+        os.makedirs(save_dir, exist_ok=True)
+        path = os.path.join(save_dir, f"{case_name}.nii.gz")
+        nifti.write_nifti(path, out, spacing)
+        print(f"{path} is saved successfully")
+        return path

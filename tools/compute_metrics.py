@@ -4,7 +4,8 @@ form of the reference's 5_compute_metrics.py.
     python tools/compute_metrics.py --pred DIR --gt DIR [--out FILE.npy] [--spacing Z Y X]
 
 Cases are the files of --pred that have a file of the same name in --gt.  Label volumes are read from .npy and .npz (the first
-array, or the one called "labels" / "seg" / "arr_0"); .nii / .nii.gz only where nibabel or SimpleITK is installed.  Prints the
+array, or the one called "labels" / "seg" / "arr_0"); .nii / .nii.gz through nibabel or SimpleITK where one is installed, else through
+segmamba_amd.nifti.read_nifti (single-file NIfTI-1 as tools/finish_predictions.py and Predictor.save_to_nii write it).  Prints the
 per-case array, then its mean and standard deviation over the cases, and saves the (cases, regions, 2) array to --out."""
 import argparse
 import os
@@ -34,7 +35,8 @@ def load_labels(path: str) -> np.ndarray:
                 import SimpleITK as sitk
                 a = sitk.GetArrayFromImage(sitk.ReadImage(path))
             except ImportError:
-                raise RuntimeError(f"{path}: reading NIfTI needs nibabel or SimpleITK; convert the volume to .npy instead") from None
+                from segmamba_amd.nifti import read_nifti
+                a = read_nifti(path)[0]                                                # the library's own reader: (z, y, x)
     a = np.squeeze(np.asarray(a))
     if a.ndim != 3:
         raise RuntimeError(f"{path}: a 3-D label volume is required, got shape {a.shape}")
