@@ -966,6 +966,73 @@ typedef struct segm_ccl_select_args {
 size_t segm_ccl_select_workspace_bytes(int64_t voxels);
 int segm_ccl_select(const segm_ccl_select_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * Preparing a case on the device (additive to ABI 10; csrc/preprocess.hip).
+ * Replaces, of the reference's light_training/preprocessing: create_nonzero_mask + get_bbox_from_mask (cropping/cropping.py:8-33; the
+ * hole filling between them is segm_ccl_* with SEGM_CCL_FILL), the crop and the `seg[(seg == 0) & ~mask] = -1` rule (:35-48),
+ * ZScoreNormalization.run (normalization/default_normalization_schemes.py:31-50) and the `np.max(seg)` / per-class counts of
+ * run_case_npy (preprocessors/default_preprocessor.py:203-210).
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_PREP_MAX_CHANNELS 8
+#define SEGM_PREP_COUNT_BINS 260
+
+/* data (channels, depth, height, width) fp32, element strides for channel, z and y, unit stride along x.
+ *   mask[z, y, x] = 1 where any channel is != 0 (NaN is, -0 is not), else 0                     (cropping.py:16-19)
+ *   bbox = [z0, y0, x0, z1, y1, x1], half-open, of the mask                                     (get_bbox_from_mask, cropping.py:33)
+ * in one pass.  An all-zero volume leaves z1 = y1 = x1 = 0.  The box of the mask is the box of the hole-filled mask (a hole is
+ * enclosed along every axis), so it does not wait for the filling.  Both outputs are OVERWRITTEN. */
+typedef struct segm_nonzero_mask_bbox_args {
+    int32_t channels, depth, height, width;
+    int64_t stride_c, stride_z, stride_y;
+    const float* data;
+    uint8_t* mask;                 /* (depth, height, width), contiguous */
+    int32_t* bbox;                 /* 6 int32 in device memory */
+    void* stream;
+} segm_nonzero_mask_bbox_args;
+int segm_nonzero_mask_bbox(const segm_nonzero_mask_bbox_args* args);
+
+enum segm_prep_seg_dtype { SEGM_PREP_SEG_NONE = 0, SEGM_PREP_SEG_F32 = 1, SEGM_PREP_SEG_U8 = 2, SEGM_PREP_SEG_I16 = 3 };
+
+/* The box [box_z, box_z + box_depth) x [box_y, ..) x [box_x, ..) of `data` (as above), of the contiguous (depth, height, width)
+ * volumes `mask` (uint8, the FILLED non-zero mask) and `seg` (seg_dtype; NULL with SEGM_PREP_SEG_NONE).
+ * The relabelled seg of a voxel: its seg value, but nonzero_label where the seg is 0 and the mask is 0 (cropping.py:43); without a
+ * seg 0 inside the mask and nonzero_label outside (cropping.py:45-48).
+ *
+ * segm_crop_stats: per channel the mean and the population standard deviation (numpy's mean() / std()) over the box, or with
+ * `masked` over the box's voxels whose relabelled seg is >= 0 (default_normalization_schemes.py:42-44).  fp64 accumulation in two
+ * passes (sum, then sum of squared deviations from the mean) with a fixed reduction order: per-workgroup partials in the
+ * workspace, one workgroup adds them in index order - two calls are bit-equal.  The results stay on the device:
+ *   stats64[0..7] mean, stats64[8..15] std, stats64[16] the voxel count; stats32[0..7] / [8..15] the same rounded to fp32.
+ * `mask` may be NULL unless `masked`.
+ *
+ * segm_crop_normalize: one launch writes
+ *   out (channels, box_depth, box_height, box_width) fp32, dense = (x - stats32 mean) / max(stats32 std, 1e-8) in fp32 arithmetic
+ *       (:49); with `masked` the voxels whose relabelled seg is < 0 are copied unchanged (:45);
+ *   seg_out (box_depth, box_height, box_width) int16 = the relabelled seg (optional);
+ *   counts[SEGM_PREP_COUNT_BINS] int64, OVERWRITTEN (optional): [l] the voxels of label l for l = 0 .. 255, [256] the negative
+ *       ones, [257] those above 255, [258] the voxels whose seg value is no integer in [-1, 32767] (written as label 0: a caller
+ *       must treat a non-zero [258] as an error), [259] 0.
+ * `mask` may be NULL when neither seg_out, counts nor `masked` is given (plain normalisation). */
+typedef struct segm_crop_args {
+    int32_t channels, depth, height, width;
+    int32_t box_z, box_y, box_x, box_depth, box_height, box_width;
+    int32_t seg_dtype, masked, nonzero_label, reserved;
+    int64_t stride_c, stride_z, stride_y;
+    const float* data;
+    const uint8_t* mask;
+    const void* seg;
+    double* stats64;               /* 17 doubles; segm_crop_stats only */
+    float* stats32;                /* 16 floats: written by segm_crop_stats, read by segm_crop_normalize */
+    float* out;                    /* segm_crop_normalize only, as seg_out and counts */
+    int16_t* seg_out;
+    int64_t* counts;
+    void* workspace;     size_t workspace_bytes;      /* segm_crop_stats only */
+    void* stream;
+} segm_crop_args;
+size_t segm_crop_stats_workspace_bytes(int32_t channels, int32_t box_depth, int32_t box_height, int32_t box_width);
+int segm_crop_stats(const segm_crop_args* args);
+int segm_crop_normalize(const segm_crop_args* args);
+
 
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);

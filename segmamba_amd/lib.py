@@ -299,6 +299,7 @@ EXPORTS = (
     "segm_seg_regions", "segm_seg_regions_workspace_bytes", "segm_edt_sq", "segm_border_distances", "segm_border_distances_workspace_bytes",
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
+    "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -371,6 +372,28 @@ class CclSelectArgs(C.Structure):
     _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
                 ("mode", C.c_int32), ("min_size", C.c_int32), ("reserved", C.c_int32),
                 ("roots", C.c_void_p), ("sizes", C.c_void_p), ("touches", C.c_void_p), ("out", C.c_void_p), ("info", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+PREP_MAX_CHANNELS, PREP_COUNT_BINS = 8, 260                                    # SEGM_PREP_MAX_CHANNELS / SEGM_PREP_COUNT_BINS
+PREP_BIN_MINUS, PREP_BIN_ABOVE, PREP_BIN_INVALID = 256, 257, 258               # the bins of segm_crop_normalize's counts past the labels
+PREP_SEG_NONE, PREP_SEG_F32, PREP_SEG_U8, PREP_SEG_I16 = 0, 1, 2, 3            # enum segm_prep_seg_dtype
+
+
+class NonzeroMaskBboxArgs(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("data", C.c_void_p), ("mask", C.c_void_p), ("bbox", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class CropArgs(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("box_z", C.c_int32), ("box_y", C.c_int32), ("box_x", C.c_int32),
+                ("box_depth", C.c_int32), ("box_height", C.c_int32), ("box_width", C.c_int32),
+                ("seg_dtype", C.c_int32), ("masked", C.c_int32), ("nonzero_label", C.c_int32), ("reserved", C.c_int32),
+                ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("data", C.c_void_p), ("mask", C.c_void_p), ("seg", C.c_void_p),
+                ("stats64", C.c_void_p), ("stats32", C.c_void_p), ("out", C.c_void_p), ("seg_out", C.c_void_p), ("counts", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
@@ -465,6 +488,10 @@ class SegmLib:
         sig("segm_ccl_sizes", [C.POINTER(CclSizesArgs)], C.c_int)
         sig("segm_ccl_select", [C.POINTER(CclSelectArgs)], C.c_int)
         sig("segm_ccl_select_workspace_bytes", [C.c_int64], C.c_size_t)
+        sig("segm_nonzero_mask_bbox", [C.POINTER(NonzeroMaskBboxArgs)], C.c_int)
+        sig("segm_crop_stats", [C.POINTER(CropArgs)], C.c_int)
+        sig("segm_crop_stats_workspace_bytes", [C.c_int32] * 4, C.c_size_t)
+        sig("segm_crop_normalize", [C.POINTER(CropArgs)], C.c_int)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

@@ -1641,6 +1641,116 @@ def ccl_select(lib: L.SegmLib, roots: torch.Tensor, sizes: torch.Tensor, mode: i
 
 
 # ---------------------------------------------------------------------------------------------------------
+# preparing a case (csrc/preprocess.hip): non-zero mask and box, crop statistics, crop + z-score + seg relabelling
+# ---------------------------------------------------------------------------------------------------------
+_SEG_DTYPES = {torch.float32: L.PREP_SEG_F32, torch.uint8: L.PREP_SEG_U8, torch.int16: L.PREP_SEG_I16}
+
+
+def _prep_data(data, what: str):
+    """(C, D, H, W) fp32 with a unit stride along x, C <= 8: -> (C, D, H, W, stride_c, stride_z, stride_y)"""
+    if not isinstance(data, torch.Tensor) or data.dim() != 4:
+        raise RuntimeError(f"{what}: data (C, D, H, W) required, got {getattr(data, 'shape', type(data))}")
+    if data.dtype != torch.float32:
+        raise RuntimeError(f"{what}: float32 data are required, got {data.dtype}")
+    C_, D, H, W = data.shape
+    if not 1 <= C_ <= L.PREP_MAX_CHANNELS or min(D, H, W) < 1:
+        raise RuntimeError(f"{what}: 1 .. {L.PREP_MAX_CHANNELS} channels and a non-empty volume, got {tuple(data.shape)}")
+    if D * H * W > L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"{what}: at most 2^31 - 1 voxels per channel, got {tuple(data.shape)}")
+    sc, sz, sy, sx = data.stride()
+    if W > 1 and sx != 1:
+        raise RuntimeError(f"{what}: data need a unit stride along the last dimension")
+    if (H > 1 and sy < W) or min(sc, sz) < 0:
+        raise RuntimeError(f"{what}: unsupported data strides {data.stride()}")
+    return C_, D, H, W, sc, sz, max(sy, W)
+
+
+def _prep_box(box_start, box_shape, shape, what: str):
+    box_start = (0, 0, 0) if box_start is None else tuple(int(v) for v in box_start)
+    box_shape = tuple(n - b for n, b in zip(shape, box_start)) if box_shape is None else tuple(int(v) for v in box_shape)
+    if len(box_start) != 3 or len(box_shape) != 3:
+        raise RuntimeError(f"{what}: box_start and box_shape have three entries each")
+    if any(bs < 1 or b0 < 0 or b0 + bs > n for b0, bs, n in zip(box_start, box_shape, shape)):
+        raise RuntimeError(f"{what}: the box {box_start} + {box_shape} does not lie inside the volume {tuple(shape)}")
+    return box_start, box_shape
+
+
+def _crop_args(data, mask, seg, box_start, box_shape, masked, nonzero_label, what: str):
+    C_, D, H, W, sc, sz, sy = _prep_data(data, what)
+    box_start, box_shape = _prep_box(box_start, box_shape, (D, H, W), what)
+    if mask is not None:
+        _same_volume(mask, f"{what}: mask", torch.uint8, (D, H, W), data.device)
+    seg_code = L.PREP_SEG_NONE
+    if seg is not None:
+        if not isinstance(seg, torch.Tensor) or seg.dtype not in _SEG_DTYPES:
+            raise RuntimeError(f"{what}: seg must be a float32, uint8 or int16 tensor, got {getattr(seg, 'dtype', type(seg))}")
+        _same_volume(seg, f"{what}: seg", seg.dtype, (D, H, W), data.device)
+        seg_code = _SEG_DTYPES[seg.dtype]
+    nonzero_label = int(nonzero_label)
+    if not -1 <= nonzero_label <= 32767:
+        raise RuntimeError(f"{what}: nonzero_label must lie in [-1, 32767], got {nonzero_label}")
+    a = L.CropArgs()
+    a.channels, a.depth, a.height, a.width = C_, D, H, W
+    a.box_z, a.box_y, a.box_x = box_start
+    a.box_depth, a.box_height, a.box_width = box_shape
+    a.seg_dtype, a.masked, a.nonzero_label = seg_code, 1 if masked else 0, nonzero_label
+    a.stride_c, a.stride_z, a.stride_y = sc, sz, sy
+    a.data, a.mask, a.seg, a.stream = data.data_ptr(), L.fptr(mask), L.fptr(seg), L.stream_handle(data)
+    return a, box_shape
+
+
+def nonzero_mask_bbox(lib: L.SegmLib, data: torch.Tensor):
+    """data (C, D, H, W) fp32 with a unit stride along x, C <= 8.  -> (mask uint8 (D, H, W): 1 where any channel is != 0 (NaN is);
+    bbox int32 (6,) on the device = [z0, y0, x0, z1, y1, x1], half-open; z1 = y1 = x1 = 0 for an all-zero volume)."""
+    C_, D, H, W, sc, sz, sy = _prep_data(data, "nonzero_mask_bbox")
+    mask = torch.empty(D, H, W, dtype=torch.uint8, device=data.device)
+    bbox = torch.empty(6, dtype=torch.int32, device=data.device)
+    a = L.NonzeroMaskBboxArgs()
+    a.channels, a.depth, a.height, a.width = C_, D, H, W
+    a.stride_c, a.stride_z, a.stride_y = sc, sz, sy
+    a.data, a.mask, a.bbox, a.stream = data.data_ptr(), mask.data_ptr(), bbox.data_ptr(), L.stream_handle(data)
+    lib.check(lib.dll.segm_nonzero_mask_bbox(a), "nonzero_mask_bbox")
+    return mask, bbox
+
+
+def crop_stats(lib: L.SegmLib, data: torch.Tensor, box_start=None, box_shape=None, mask: torch.Tensor = None, seg: torch.Tensor = None,
+               masked: bool = False, nonzero_label: int = -1):
+    """Per-channel mean and population std of data (C, D, H, W) over the box (default: the volume), with `masked` over the box's
+    voxels whose relabelled seg is >= 0 (mask: the filled non-zero mask, uint8 (D, H, W); seg: float32 / uint8 / int16 (D, H, W) or
+    None).  fp64, fixed order.  -> (stats64 float64 (17,): mean [0:8], std [8:16], voxel count [16]; stats32 float32 (16,)), on the device."""
+    if masked and mask is None:
+        raise RuntimeError("crop_stats: the masked form needs the mask")
+    a, box_shape = _crop_args(data, mask, seg, box_start, box_shape, masked, nonzero_label, "crop_stats")
+    stats64 = torch.zeros(17, dtype=torch.float64, device=data.device)
+    stats32 = torch.zeros(16, dtype=torch.float32, device=data.device)
+    nbytes = lib.dll.segm_crop_stats_workspace_bytes(a.channels, *box_shape)
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=data.device)
+    a.stats64, a.stats32, a.workspace, a.workspace_bytes = stats64.data_ptr(), stats32.data_ptr(), ws.data_ptr(), nbytes
+    lib.check(lib.dll.segm_crop_stats(a), "crop_stats")
+    return stats64, stats32
+
+
+def crop_normalize(lib: L.SegmLib, data: torch.Tensor, stats32: torch.Tensor, box_start=None, box_shape=None, mask: torch.Tensor = None,
+                   seg: torch.Tensor = None, masked: bool = False, nonzero_label: int = -1, want_seg: bool = True):
+    """The box of data (C, D, H, W), normalised with `stats32` (as `crop_stats` gives it): (x - mean) / max(std, 1e-8) in fp32; with
+    `masked` the voxels whose relabelled seg is < 0 are copied.  With `want_seg` (needs the mask) also the relabelled seg and its label
+    counts.  -> (out float32 (C, d, h, w), seg_out int16 (d, h, w) or None, counts int64 (260,) on the device or None)."""
+    if (want_seg or masked) and mask is None:
+        raise RuntimeError("crop_normalize: the relabelled seg and the masked form need the mask")
+    a, box_shape = _crop_args(data, mask, seg, box_start, box_shape, masked, nonzero_label, "crop_normalize")
+    _same_volume(stats32, "crop_normalize: stats32", torch.float32, (16,), data.device)
+    out = torch.empty((a.channels,) + box_shape, dtype=torch.float32, device=data.device)
+    seg_out = counts = None
+    if want_seg:
+        seg_out = torch.empty(box_shape, dtype=torch.int16, device=data.device)
+        counts = torch.empty(L.PREP_COUNT_BINS, dtype=torch.int64, device=data.device)
+        a.seg_out, a.counts = seg_out.data_ptr(), counts.data_ptr()
+    a.stats32, a.out = stats32.data_ptr(), out.data_ptr()
+    lib.check(lib.dll.segm_crop_normalize(a), "crop_normalize")
+    return out, seg_out, counts
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -1683,5 +1793,6 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "instnorm_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
-              "space_to_depth2", "seg_regions", "edt_sq", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select"):
+              "space_to_depth2", "seg_regions", "edt_sq", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
+              "nonzero_mask_bbox", "crop_stats", "crop_normalize"):
     globals()[_name] = _device_guard(globals()[_name])
