@@ -1033,6 +1033,56 @@ size_t segm_crop_stats_workspace_bytes(int32_t channels, int32_t box_depth, int3
 int segm_crop_stats(const segm_crop_args* args);
 int segm_crop_normalize(const segm_crop_args* args);
 
+/* ------------------------------------------------------------------------------------------------
+ * Resampling a case to the target spacing (additive to ABI 10; csrc/resample.hip).
+ * Replaces the reference's resample_data_or_seg without a separate z axis (light_training/preprocessing/resampling/
+ * default_resampling.py:126-217 as default_preprocessor.py:187-201 calls it): skimage's resize(order 3 or 1, mode='edge',
+ * anti_aliasing=False, clip=True) for the data - for n-D input scipy.ndimage.zoom(mode='nearest', grid_mode=True) - and
+ * batchgenerators' resize_segmentation(order 1) for the seg.  Non-finite input values are outside the contract.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_ZOOM_MAX_SIDE 2048
+
+/* data (channels, depth, height, width) fp32, element strides for channel, z and y, unit stride along x ->
+ * out (channels, out_depth, out_height, out_width) fp32, dense.  Output voxel i of an axis samples the input at
+ * (i + 0.5) * (n_in / n_out) - 0.5.
+ *   order 3: cubic B-spline.  Per axis the line is padded by 12 edge copies, multiplied by 6 and run through the causal and
+ *            anti-causal recursion with the pole sqrt(3) - 2 under mirror boundary conditions (scipy's spline_filter on the padded
+ *            array); the coefficients are kept in fp64 in the workspace, the 64 taps of an output are summed in fp64.
+ *   order 1: trilinear, the coordinate clamped to [0, n_in - 1]; fp64 arithmetic on the fp32 input.
+ * clip = 1 clamps every channel to the minimum and maximum of its own input, found on the device (skimage's clip=True); then the
+ * result is rounded to fp32.  Sums have a fixed order and there are no floating-point atomics: two calls are bit-equal.
+ * Limits (SEGM_E_SHAPE, nothing is launched): channels in [1, SEGM_PREP_MAX_CHANNELS]; every side, in and out, in
+ * [1, SEGM_ZOOM_MAX_SIDE]; fewer than 2^31 voxels per channel, in and out; order 1 or 3; clip 0 or 1.
+ * Workspace: 256 bytes, and for order 3 channels * (depth + 4) * (height + 4) * (width + 4) doubles behind them. */
+typedef struct segm_zoom_args {
+    int32_t channels, depth, height, width;
+    int32_t out_depth, out_height, out_width;
+    int32_t order, clip, reserved;
+    int64_t stride_c, stride_z, stride_y;
+    const float* data;
+    float* out;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_zoom_args;
+size_t segm_zoom_workspace_bytes(int32_t channels, int32_t depth, int32_t height, int32_t width, int32_t order);
+int segm_zoom(const segm_zoom_args* args);
+
+/* seg (depth, height, width) int16, contiguous (what segm_crop_normalize writes: labels >= -1) -> out (out_depth, out_height,
+ * out_width) int16.  Per output voxel the trilinear weights of its 8 corners (coordinates as order 1 above, fp64) are summed per
+ * distinct corner label; the largest label whose sum is >= 0.5 wins, 0 if there is none - resize_segmentation's
+ * `out[resize(seg == c) >= 0.5] = c` over the labels in ascending order.  Label -1 takes part like any other.
+ * counts[SEGM_PREP_COUNT_BINS] int64, OVERWRITTEN (optional): the labels of `out` in segm_crop_normalize's layout ([258] and [259] 0).
+ * Limits as for segm_zoom. */
+typedef struct segm_zoom_labels_args {
+    int32_t depth, height, width;
+    int32_t out_depth, out_height, out_width;
+    const int16_t* seg;
+    int16_t* out;
+    int64_t* counts;
+    void* stream;
+} segm_zoom_labels_args;
+int segm_zoom_labels(const segm_zoom_labels_args* args);
+
 
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);

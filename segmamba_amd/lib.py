@@ -300,6 +300,7 @@ EXPORTS = (
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
+    "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -397,6 +398,24 @@ class CropArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+ZOOM_MAX_SIDE = 2048                                                           # SEGM_ZOOM_MAX_SIDE
+
+
+class ZoomArgs(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("out_depth", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
+                ("order", C.c_int32), ("clip", C.c_int32), ("reserved", C.c_int32),
+                ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("data", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class ZoomLabelsArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("out_depth", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
+                ("seg", C.c_void_p), ("out", C.c_void_p), ("counts", C.c_void_p), ("stream", C.c_void_p)]
+
+
 def header_abi_version() -> int:
     """SEGM_ABI_VERSION as include/segmamba_hip.h declares it (what a freshly built library must report)"""
     import re
@@ -492,6 +511,9 @@ class SegmLib:
         sig("segm_crop_stats", [C.POINTER(CropArgs)], C.c_int)
         sig("segm_crop_stats_workspace_bytes", [C.c_int32] * 4, C.c_size_t)
         sig("segm_crop_normalize", [C.POINTER(CropArgs)], C.c_int)
+        sig("segm_zoom", [C.POINTER(ZoomArgs)], C.c_int)
+        sig("segm_zoom_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
+        sig("segm_zoom_labels", [C.POINTER(ZoomLabelsArgs)], C.c_int)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

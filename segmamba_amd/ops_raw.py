@@ -1751,6 +1751,63 @@ def crop_normalize(lib: L.SegmLib, data: torch.Tensor, stats32: torch.Tensor, bo
 
 
 # ---------------------------------------------------------------------------------------------------------
+# resampling a case (csrc/resample.hip): cubic / linear zoom of the data, the label rule for the seg
+# ---------------------------------------------------------------------------------------------------------
+def _zoom_shape(shape, what: str):
+    shape = tuple(int(v) for v in shape)
+    if len(shape) != 3:
+        raise RuntimeError(f"{what}: the new shape has three entries, got {shape}")
+    if any(not 1 <= n <= L.ZOOM_MAX_SIDE for n in shape):
+        raise RuntimeError(f"{what}: every side must lie in [1, {L.ZOOM_MAX_SIDE}], got {shape}")
+    if shape[0] * shape[1] * shape[2] > L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"{what}: at most 2^31 - 1 voxels per channel, got {shape}")
+    return shape
+
+
+def zoom(lib: L.SegmLib, data: torch.Tensor, new_shape, order: int = 3, clip: bool = True) -> torch.Tensor:
+    """data (C, D, H, W) fp32 with a unit stride along x, C <= 8 -> (C,) + new_shape fp32: skimage's `resize(order, mode='edge',
+    anti_aliasing=False, clip=clip)` per channel (scipy.ndimage.zoom with mode='nearest', grid_mode=True).  order 3 (cubic B-spline,
+    fp64 coefficients in a workspace of C (D + 4) (H + 4) (W + 4) doubles) or 1 (trilinear).  Sides up to 2048; two calls are bit-equal."""
+    C_, D, H, W, sc, sz, sy = _prep_data(data, "zoom")
+    _zoom_shape((D, H, W), "zoom: data")
+    new_shape = _zoom_shape(new_shape, "zoom")
+    if order not in (1, 3):
+        raise RuntimeError(f"zoom: order 1 or 3, got {order}")
+    nbytes = lib.dll.segm_zoom_workspace_bytes(C_, D, H, W, order)
+    if nbytes == 0:
+        raise RuntimeError(f"zoom: no workspace size for {tuple(data.shape)}, order {order}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=data.device)
+    out = torch.empty((C_,) + new_shape, dtype=torch.float32, device=data.device)
+    a = L.ZoomArgs()
+    a.channels, a.depth, a.height, a.width = C_, D, H, W
+    a.out_depth, a.out_height, a.out_width = new_shape
+    a.order, a.clip = order, 1 if clip else 0
+    a.stride_c, a.stride_z, a.stride_y = sc, sz, sy
+    a.data, a.out, a.workspace, a.workspace_bytes, a.stream = data.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(data)
+    lib.check(lib.dll.segm_zoom(a), "zoom")
+    return out
+
+
+def zoom_labels(lib: L.SegmLib, seg: torch.Tensor, new_shape, want_counts: bool = True):
+    """seg (D, H, W) int16, contiguous -> (new_shape int16, counts int64 (260,) on the device or None): batchgenerators'
+    `resize_segmentation(seg, new_shape, 1)` - the largest label whose trilinear weight is >= 0.5, else 0 - and the label counts of
+    the result in `crop_normalize`'s layout."""
+    if not isinstance(seg, torch.Tensor) or seg.dim() != 3:
+        raise RuntimeError(f"zoom_labels: a (D, H, W) seg is required, got {getattr(seg, 'shape', type(seg))}")
+    _same_volume(seg, "zoom_labels: seg", torch.int16, tuple(seg.shape), seg.device)
+    D, H, W = _zoom_shape(seg.shape, "zoom_labels: seg")
+    new_shape = _zoom_shape(new_shape, "zoom_labels")
+    out = torch.empty(new_shape, dtype=torch.int16, device=seg.device)
+    counts = torch.empty(L.PREP_COUNT_BINS, dtype=torch.int64, device=seg.device) if want_counts else None
+    a = L.ZoomLabelsArgs()
+    a.depth, a.height, a.width = D, H, W
+    a.out_depth, a.out_height, a.out_width = new_shape
+    a.seg, a.out, a.counts, a.stream = seg.data_ptr(), out.data_ptr(), L.fptr(counts), L.stream_handle(seg)
+    lib.check(lib.dll.segm_zoom_labels(a), "zoom_labels")
+    return out, counts
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -1794,5 +1851,5 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
               "space_to_depth2", "seg_regions", "edt_sq", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
-              "nonzero_mask_bbox", "crop_stats", "crop_normalize"):
+              "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels"):
     globals()[_name] = _device_guard(globals()[_name])

@@ -1,16 +1,19 @@
-"""Preparing a case on the device: non-zero crop, z-score normalisation, class locations (csrc/preprocess.hip).
+"""Preparing a case on the device: non-zero crop, z-score normalisation, resampling, class locations (csrc/preprocess.hip, csrc/resample.hip).
 
 The stage of the reference's pipeline in front of training (2_preprocessing_mri.py on light_training/preprocessing):
 `MultiModalityPreprocessor.run_case_npy` (preprocessors/default_preprocessor.py:154-227 through preprocessor_mri.py) - the non-zero
 mask over the channels, its holes filled, the bounding box, the crop of data and seg with `seg[(seg == 0) & ~mask] = -1`, the
-per-channel z-score, the class locations that the patch sampler draws foreground from, and the `properties` that
+per-channel z-score, the resampling to the target spacing (`resample=True`; segmamba_amd/resample.py), the class locations that
+the patch sampler draws foreground from, and the `properties` that
 `postprocess.labels_from_logits` and `Predictor.predict_labels` take back.  The functions carry the reference's names.  Tensors stay
 on the device; numpy arrays and host tensors are uploaded.  A case costs two scalars-only readbacks before its class locations are
 drawn - the box (6 ints) and the label counts (260 ints); nothing volume-sized goes back to the host except what is written to disk.
 
 Limits and where this deliberately differs from the reference:
-  * a case whose `compute_new_shape` differs from its crop shape raises NotImplementedError: the order-3 spline resampling of
-    skimage's `resize` is not part of this module (every BraTS case is 1 mm in, [1, 1, 1] out: the reference returns it unchanged);
+  * resampling is opt-in: by default a case whose `compute_new_shape` differs from its crop shape raises NotImplementedError (every
+    BraTS case is 1 mm in, [1, 1, 1] out: the reference returns it unchanged).  With `resample=True` the normalised crop goes through
+    the order-3 spline zoom and the relabelled seg through the order-1 label rule, as the reference's `run_case_npy` does; the
+    limits and the rounding-level deviations of that step are stated in segmamba_amd/resample.py;
   * an all-zero volume raises RuntimeError (the reference fails inside `get_bbox_from_mask`);
   * `intensities_per_channel` and `intensity_statistics_per_channel` are not produced (the reference comments that it does not use
     them; the z-score never reads them);
@@ -33,6 +36,7 @@ from . import lib as L
 from . import ops_raw
 from .metrics import _to_device
 from .postprocess import _fill
+from .resample import compute_new_shape            # noqa: F401  (resampling/default_resampling.py:23-30)
 
 NUM_SAMPLES = 10000                   # _sample_foreground_locations (default_preprocessor.py:456-457)
 MIN_PERCENT_COVERAGE = 0.01
@@ -163,16 +167,14 @@ def sample_foreground_locations(seg, classes_or_regions, seed: int = 1234, count
     return class_locs
 
 
-def compute_new_shape(old_shape, old_spacing, new_spacing):
-    """resampling/default_resampling.py:23-30"""
-    return [int(round(i / j * k)) for i, j, k in zip(old_spacing, new_spacing, old_shape)]
-
-
-def preprocess_case(data, seg, properties: dict, out_spacing=(1, 1, 1), all_labels=(1, 2, 3), use_mask_for_norm: bool = False):
+def preprocess_case(data, seg, properties: dict, out_spacing=(1, 1, 1), all_labels=(1, 2, 3), use_mask_for_norm: bool = False,
+                    resample: bool = False):
     """`run_case_npy` (default_preprocessor.py:154-227).  data (C, D, H, W); seg (1, D, H, W) / (D, H, W) or None; properties with
     `spacing` (SimpleITK's (x, y, z)).  -> (data (C, d, h, w) fp32, seg (1, d, h, w) int8 / int16) on the device; `properties` gains
     original_spacing_trans, target_spacing_trans, shape_before_cropping, bbox_used_for_cropping, shape_after_cropping_before_resample,
-    shape_after_resample (plain ints, floats and lists) and class_locations (`sample_foreground_locations`)."""
+    shape_after_resample (plain ints, floats and lists) and class_locations (`sample_foreground_locations`).  With `resample` a crop
+    whose `compute_new_shape` differs from its shape is resampled to it (data order 3, seg order 1: default_preprocessor.py:187-201);
+    the class locations and the seg's dtype then come from the resampled seg.  Without it such a case raises NotImplementedError."""
     lib = L.get_lib()
     d = _data(data, "preprocess_case")
     s = _seg(seg, d.shape[1:], "preprocess_case")
@@ -181,12 +183,18 @@ def preprocess_case(data, seg, properties: dict, out_spacing=(1, 1, 1), all_labe
     filled, bbox = _box(lib, d)
     crop_shape = [b[1] - b[0] for b in bbox]
     new_shape = compute_new_shape(crop_shape, spacing_trans, target)
-    if new_shape != crop_shape:
+    if new_shape != crop_shape and not resample:
         raise NotImplementedError(f"preprocess_case: the crop of shape {crop_shape} would be resampled to {new_shape} (spacing "
-                                  f"{spacing_trans} -> {target}); spline resampling is not part of this module")
+                                  f"{spacing_trans} -> {target}); spline resampling is not part of this module unless resample=True is given")
     start = [b[0] for b in bbox]
     _, stats32 = ops_raw.crop_stats(lib, d, start, crop_shape, mask=filled, seg=s, masked=use_mask_for_norm)
     out, seg_out, counts = ops_raw.crop_normalize(lib, d, stats32, start, crop_shape, mask=filled, seg=s, masked=use_mask_for_norm)
+    if new_shape != crop_shape:
+        # an invalid seg value was written as label 0 and would be lost in the zoom: the first counts flag it (on the device)
+        invalid = counts[L.PREP_BIN_INVALID]
+        out = ops_raw.zoom(lib, out, new_shape, 3, True)
+        seg_out, counts = ops_raw.zoom_labels(lib, seg_out, new_shape)
+        counts[L.PREP_BIN_INVALID] = invalid
     c, top = _check_counts(counts)
     properties["original_spacing_trans"] = spacing_trans
     properties["target_spacing_trans"] = target
@@ -203,10 +211,11 @@ class CasePreprocessor:
     one NIfTI file per modality (`data_filenames`) and optionally the seg (`seg_filename`).  `run` writes the reference's
     `<case>.npz` (data, seg) and `<case>.pkl` (properties) into `output_dir`, one case after the other."""
 
-    def __init__(self, base_dir, image_dir, data_filenames: Sequence[str] = (), seg_filename: str = "", use_mask_for_norm: bool = False):
+    def __init__(self, base_dir, image_dir, data_filenames: Sequence[str] = (), seg_filename: str = "", use_mask_for_norm: bool = False,
+                 resample: bool = False):
         self.base_dir, self.image_dir = str(base_dir), str(image_dir)
         self.data_filenames, self.seg_filename = list(data_filenames), seg_filename
-        self.use_mask_for_norm = use_mask_for_norm
+        self.use_mask_for_norm, self.resample = use_mask_for_norm, resample
         self.out_spacing, self.all_labels, self.output_dir = (1, 1, 1), (1, 2, 3), None
 
     def get_iterable_list(self):
@@ -231,7 +240,7 @@ class CasePreprocessor:
 
     def run_case(self, case_name):
         data, seg, properties = self.read_data(case_name)
-        data, seg = preprocess_case(data, seg, properties, self.out_spacing, self.all_labels, self.use_mask_for_norm)
+        data, seg = preprocess_case(data, seg, properties, self.out_spacing, self.all_labels, self.use_mask_for_norm, self.resample)
         return data, seg, properties
 
     def run_case_save(self, case_name):

@@ -108,5 +108,13 @@ mq = ops_raw.conv3d_cube_index(emu, 192, 64, False, "cpu")
 ops_raw.gather16(emu, wq.reshape(-1), mq, torch.empty(mq.numel(), dtype=torch.bfloat16))
 ops_raw.gather16(emu, wq.reshape(-1), ops_raw.gather16_compact_map(mq), torch.empty(mq.numel(), dtype=torch.bfloat16), compact=True)
 print("gather16 ok", flush=True)
+# resampling: a side of 1, a side above one 256-voxel tile of the x prefilter, up- and down-sampling, a strided channel view
+for shp, new in (((5, 1, 9), (7, 3, 18)), ((3, 4, 300), (2, 6, 150)), ((6, 7, 8), (9, 7, 4))):
+    xz = torch.randn(3, shp[0], shp[1], shp[2] + 5, generator=g)[:, :, :, 2:-3]
+    for order in (3, 1):
+        ops_raw.zoom(emu, xz, new, order, True); ops_raw.zoom(emu, xz[::2], new, order, False)
+    sz = torch.randint(-1, 4, shp, generator=g).to(torch.int16)
+    ops_raw.zoom_labels(emu, sz, new); ops_raw.zoom_labels(emu, sz, new, want_counts=False)
+print("zoom / zoom_labels ok", flush=True)
 print("AddressSanitizer run finished without reports")
 PY
