@@ -1084,6 +1084,102 @@ typedef struct segm_zoom_labels_args {
 int segm_zoom_labels(const segm_zoom_labels_args* args);
 
 
+/* ------------------------------------------------------------------------------------------------
+ * Training augmentation at the reference's interpolation orders (additive to ABI 10; csrc/augment.hip).
+ * The stencil / gather transforms of the reference's get_train_transforms (light_training/augment/train_augment.py:29-50) as
+ * batchgenerators runs them through scipy: SpatialTransform with order_data=3 / order_seg=1, SimulateLowResolution's nearest
+ * down-sampling, GaussianBlur.  A launch takes a batch (samples, channels, depth, height, width) fp32 with element strides for
+ * sample, channel, z and y and unit stride along x; at most SEGM_AUG_MAX_SAMPLES samples and SEGM_PREP_MAX_CHANNELS channels; every
+ * side in [1, SEGM_ZOOM_MAX_SIDE]; fewer than 2^31 voxels per volume.  Matrices, sigmas and on / off flags travel by value in the
+ * argument structs: no call copies anything to the device.  Sums have a fixed order and there are no floating-point atomics: two
+ * calls are bit-equal.  Non-finite input values are outside the contract.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_AUG_MAX_SAMPLES 8
+#define SEGM_AUG_MAX_VOLUMES (SEGM_AUG_MAX_SAMPLES * SEGM_PREP_MAX_CHANNELS)
+#define SEGM_BLUR_MAX_RADIUS 4
+
+/* Cubic B-spline coefficients of every volume of the samples whose `on` flag is set, fp64, into the dense workspace
+ * (samples, channels, depth, height, width): scipy.ndimage.spline_filter(x, 3, output=float64, mode='mirror'), which is what
+ * map_coordinates(order=3, mode='constant') filters with - gain 6, the causal and the anti-causal recursion with the pole
+ * sqrt(3) - 2 under mirror boundary conditions on the bare line, axes of length 1 left alone.  Volumes of samples that are off
+ * are not written.  Workspace: samples * channels * depth * height * width doubles. */
+typedef struct segm_spline_coefs_args {
+    int32_t samples, channels, depth, height, width, reserved;
+    int64_t stride_n, stride_c, stride_z, stride_y;
+    uint8_t on[SEGM_AUG_MAX_SAMPLES];
+    const float* data;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_spline_coefs_args;
+size_t segm_spline_coefs_workspace_bytes(int32_t samples, int32_t channels, int32_t depth, int32_t height, int32_t width);
+int segm_spline_coefs(const segm_spline_coefs_args* args);
+
+/* out (samples, channels, depth, height, width) fp32, dense.  Output voxel (z, y, x) of sample n samples the input at
+ * p = A_n (z, y, x)^T + t_n, matrix[n] = the rows [A | t] of a 3 x 4 fp64 matrix.  If a component of p is < 0 or > side - 1 the
+ * output is cval; otherwise the 64 taps of the cubic B-spline around p are gathered from `coefs` (what segm_spline_coefs wrote),
+ * tap indices outside the line mirrored, summed in fp64 and rounded once to fp32 - batchgenerators' interpolate_img:
+ * map_coordinates(x.astype(float64), p, order=3, mode='constant', cval).astype(float32).  Every channel of a sample shares the
+ * sample's coordinates.  Samples that are off are copied from `data` bit for bit (their coefficients are not read). */
+typedef struct segm_affine_spline3_args {
+    int32_t samples, channels, depth, height, width, reserved;
+    int64_t stride_n, stride_c, stride_z, stride_y;      /* of data */
+    double matrix[SEGM_AUG_MAX_SAMPLES][12];
+    float cval;          int32_t reserved2;
+    uint8_t on[SEGM_AUG_MAX_SAMPLES];
+    const float* data;
+    const double* coefs;
+    float* out;
+    void* stream;
+} segm_affine_spline3_args;
+int segm_affine_spline3(const segm_affine_spline3_args* args);
+
+/* seg, out (samples, depth, height, width) int16 (wide = 0) or int64 (wide = 1), dense; matrices as above.  Outside the volume the
+ * output is 0; inside, the trilinear weights of the 8 corners are summed per distinct corner label in fp64 and the largest label
+ * whose sum is >= 0.5 wins, 0 if none does - batchgenerators' interpolate_img(is_seg=True, order=1, cval=-1):
+ * result[map_coordinates(seg == c, order=1, mode='constant', cval=-1) >= 0.5] = c over the labels in ascending order, on zeros.
+ * Samples that are off are copied. */
+typedef struct segm_affine_labels_args {
+    int32_t samples, depth, height, width, wide, reserved;
+    double matrix[SEGM_AUG_MAX_SAMPLES][12];
+    uint8_t on[SEGM_AUG_MAX_SAMPLES];
+    const void* seg;
+    void* out;
+    void* stream;
+} segm_affine_labels_args;
+int segm_affine_labels(const segm_affine_labels_args* args);
+
+/* Order-0 zoom: data (channels, depth, height, width) fp32 (strides as segm_zoom) -> out (channels, out_depth, out_height,
+ * out_width), dense - scipy.ndimage.zoom(order=0, mode='nearest', grid_mode=True), skimage's resize(order=0, mode='edge',
+ * anti_aliasing=False) as SimulateLowResolutionTransform calls it.  Per axis output i takes input
+ * clamp(floor((i + 0.5) * (n_in / n_out) - 0.5 + 0.5), 0, n_in - 1), in fp64. */
+typedef struct segm_zoom_nearest_args {
+    int32_t channels, depth, height, width;
+    int32_t out_depth, out_height, out_width, reserved;
+    int64_t stride_c, stride_z, stride_y;
+    const float* data;
+    float* out;
+    void* stream;
+} segm_zoom_nearest_args;
+int segm_zoom_nearest(const segm_zoom_nearest_args* args);
+
+/* scipy.ndimage.gaussian_filter(x_fp32, sigma) of every volume whose `on` flag is set (volume v = sample * channels + channel):
+ * radius int(4 sigma + 0.5) <= SEGM_BLUR_MAX_RADIUS, weights exp(-0.5 (t / sigma)^2) normalised in fp64, boundary 'reflect'
+ * (d c b a | a b c d), the axes in the order z, y, x, each pass summed in fp64 (centre first, then the pairs from the outermost
+ * inwards, as scipy's symmetric correlate1d) and rounded to fp32.  Volumes that are off are copied to `out` and take no part in the
+ * second and third pass.  out (samples, channels, depth, height, width) fp32, dense; workspace: as many bytes as `out`. */
+typedef struct segm_gauss_blur_args {
+    int32_t samples, channels, depth, height, width, reserved;
+    int64_t stride_n, stride_c, stride_z, stride_y;
+    double sigma[SEGM_AUG_MAX_VOLUMES];
+    uint8_t on[SEGM_AUG_MAX_VOLUMES];
+    const float* data;
+    float* out;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_gauss_blur_args;
+int segm_gauss_blur(const segm_gauss_blur_args* args);
+
+
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);
 const char* segm_status_string(int status);

@@ -28,13 +28,18 @@ is restated from its published implementation:
   Mirror                   each of the three axes with p 0.5, image and label together
 
 Every random decision comes from one torch.Generator on the device (reproducible per rank: seed 42 + rank, trainer.py:331).
+`SplineAugmenter` below runs the same chain at the reference's interpolation orders on the kernels of csrc/augment.hip.
 """
 from __future__ import annotations
 
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
+
+from . import lib as L
+from . import ops_raw
 
 
 class DeviceAugmenter:
@@ -159,3 +164,206 @@ class DeviceAugmenter:
                 x = torch.where(flip[:, None, None, None, None], x.flip(2 + ax), x)
                 y = torch.where(flip[:, None, None, None], y.flip(1 + ax), y)
         return x.contiguous(), y.contiguous()
+
+
+class SplineAugmenter:
+    """The chain of `DeviceAugmenter` with the three stencil / gather transforms at the reference's interpolation orders, on the
+    kernels of csrc/augment.hip, and with every decision drawn on the host.  Same call signature, output shapes and dtypes.
+
+      SpatialTransform       data: cubic spline, `map_coordinates(order=3, mode='constant', cval=0)` on fp64 coefficients
+                             (`ops_raw.spline_coefs` -> `affine_spline3`); label: linear per label with the `>= 0.5` rule
+                             (`affine_labels`, 0 outside the volume).  Output voxel (z, y, x) of a sample reads the input at
+                             M ((z, y, x) - c) + c, c = (n - 1) / 2, M = s (Rx Ry Rz)^T with
+                             Rx = [[1,0,0],[0,c,-s],[0,s,c]], Ry = [[c,0,s],[0,1,0],[-s,0,c]], Rz = [[c,-s,0],[s,c,0],[0,0,1]]:
+                             batchgenerators' create_zero_centered_coordinate_mesh / rotate_coords_3d / scale_coords with
+                             random_crop=False, restated from the published source (batchgenerators is not in the reference tree).
+                             Angles U(-30 deg, 30 deg) for the three axes with p 0.2 per sample, scale two-sided on (0.7, 1.4)
+                             with p 0.2 per sample; a sample with neither passes through bit-equal.
+      GaussianBlur           `scipy.ndimage.gaussian_filter` (truncate 4 sigma, reflect, fp32 between the passes): `gauss_blur`;
+                             p 0.2 per sample, 0.5 per channel, sigma U(0.5, 1) per channel
+      SimulateLowResolution  p 0.25 per sample, 0.5 per channel, zoom U(0.5, 1) per channel: `zoom_nearest` down to
+                             round(shape * zoom), `ops_raw.zoom(order=3, clip=True)` back up
+      noise, brightness, contrast, the two gammas, mirror: `DeviceAugmenter`'s ATen arithmetic, per sample that is on
+
+    Every coin and every scalar parameter comes from one `np.random.RandomState(seed)` on the host (`draw`), so the host knows which
+    transforms are on, launches only those and passes their parameters by value: a call copies nothing from the device and never
+    waits for it.  Only the Gaussian noise field comes from a device generator.  The stream of draws differs from
+    `DeviceAugmenter`'s: the two classes give different augmentations for one seed.  Batches of more than 8 samples or 8 channels go
+    to the kernels in groups.  fp64 coefficients of the samples that are warped: B x C x D x H x W x 8 bytes (134 MB at 2 x 4 x 128^3).
+    Needs the HIP library: tensors that are not on the device raise RuntimeError."""
+
+    def __init__(self, device, seed: int = 42, mirror_axes=(0, 1, 2), spatial: bool = True):
+        self.rs = np.random.RandomState(seed)
+        self.g = torch.Generator(device=device).manual_seed(seed)
+        self.device = torch.device(device)
+        self.mirror_axes = tuple(mirror_axes or ())
+        self.spatial = spatial
+
+    # ---- host draws -------------------------------------------------------------------------------------------------------------------
+    def _coin(self, name, p, *shape):
+        """`name` tells a subclass which transform asks (tests force single transforms on)"""
+        return self.rs.random_sample(shape) < p
+
+    def _u(self, lo, hi, *shape):
+        return lo + (hi - lo) * self.rs.random_sample(shape)
+
+    def _two_sided(self, lo, hi, *shape):
+        low, high = self._u(lo, 1.0, *shape), self._u(max(lo, 1.0), hi, *shape)
+        return np.where(self.rs.random_sample(shape) < 0.5, low, high)
+
+    @staticmethod
+    def matrix(angles, scale, shape):
+        """[A | t] (3, 4) float64 of one sample: output index (z, y, x) -> input coordinate"""
+        cx, sx, cy, sy, cz, sz = (f(a) for a in angles for f in (math.cos, math.sin))
+        Rx = np.array([[1, 0, 0], [0, cx, -sx], [0, sx, cx]], dtype=np.float64)
+        Ry = np.array([[cy, 0, sy], [0, 1, 0], [-sy, 0, cy]], dtype=np.float64)
+        Rz = np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1]], dtype=np.float64)
+        M = float(scale) * (Rx @ Ry @ Rz).T
+        ctr = (np.asarray(shape, dtype=np.float64) - 1.0) / 2.0
+        return np.concatenate([M, (ctr - M @ ctr)[:, None]], 1)
+
+    def draw(self, B, C, shape):
+        """All decisions and parameters of one call, as host values, in the order of the chain."""
+        plan = {}
+        if self.spatial:
+            rot, scl = self._coin("rotation", 0.2, B), self._coin("scale", 0.2, B)
+            angles = self._u(-math.pi / 6, math.pi / 6, B, 3) * rot[:, None]
+            scale = np.where(scl, self._two_sided(0.7, 1.4, B), 1.0)
+            plan["spatial_on"] = rot | scl
+            plan["matrices"] = np.stack([self.matrix(angles[b], scale[b], shape) for b in range(B)])
+        plan["noise_on"], plan["noise_scale"] = self._coin("noise", 0.1, B), self._u(0.0, 0.1, B)
+        plan["blur_on"] = self._coin("blur", 0.2, B)[:, None] & self._coin("blur_channel", 0.5, B, C)
+        plan["blur_sigma"] = self._u(0.5, 1.0, B, C)
+        plan["bright_on"], plan["bright"] = self._coin("brightness", 0.15, B), self._u(0.75, 1.25, B, C)
+        plan["contrast_on"], plan["contrast"] = self._coin("contrast", 0.15, B), self._two_sided(0.75, 1.25, B, C)
+        plan["lowres_on"] = self._coin("lowres", 0.25, B)[:, None] & self._coin("lowres_channel", 0.5, B, C)
+        zoom = self._u(0.5, 1.0, B, C)
+        plan["lowres_zoom"] = zoom
+        plan["lowres_shape"] = np.maximum(np.round(np.asarray(shape)[None, None] * zoom[:, :, None]).astype(int), 1)
+        plan["gamma_inv_on"], plan["gamma_inv"] = self._coin("gamma_inverted", 0.1, B), self._two_sided(0.7, 1.5, B, C)
+        plan["gamma_on"], plan["gamma"] = self._coin("gamma", 0.3, B), self._two_sided(0.7, 1.5, B, C)
+        plan["mirror"] = np.stack([self._coin("mirror", 0.5, B) for _ in self.mirror_axes], 1) if self.mirror_axes else np.zeros((B, 0), bool)
+        return plan
+
+    # ---- transforms on the kernels ------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _groups(n, size):
+        return [slice(i, min(i + size, n)) for i in range(0, n, size)]
+
+    def _spatial(self, lib, x, y, plan):
+        on = plan["spatial_on"]
+        if not on.any():
+            return x, y
+        B, C = x.shape[:2]
+        xs, ys = [], []
+        for sb in self._groups(B, L.AUG_MAX_SAMPLES):
+            flags, mats = on[sb].tolist(), plan["matrices"][sb]
+            if not any(flags):
+                xs.append(x[sb])
+                ys.append(y[sb])
+                continue
+            parts = []
+            for sc in self._groups(C, L.PREP_MAX_CHANNELS):
+                part = x[sb, sc]
+                parts.append(ops_raw.affine_spline3(lib, part, ops_raw.spline_coefs(lib, part, flags), mats, flags))
+            xs.append(parts[0] if len(parts) == 1 else torch.cat(parts, 1))
+            seg = y[sb]
+            if seg.dtype not in (torch.int16, torch.int64):
+                ys.append(ops_raw.affine_labels(lib, seg.long().contiguous(), mats, flags).to(seg.dtype))
+            else:
+                ys.append(ops_raw.affine_labels(lib, seg.contiguous(), mats, flags))
+        return (xs[0] if len(xs) == 1 else torch.cat(xs)), (ys[0] if len(ys) == 1 else torch.cat(ys))
+
+    def _blur(self, lib, x, plan):
+        on, sigma = plan["blur_on"], plan["blur_sigma"]
+        if not on.any():
+            return x
+        B, C = x.shape[:2]
+        rows = []
+        for sb in self._groups(B, L.AUG_MAX_SAMPLES):
+            parts = [ops_raw.gauss_blur(lib, x[sb, sc], sigma[sb, sc].reshape(-1).tolist(), on[sb, sc].reshape(-1).tolist())
+                     if on[sb, sc].any() else x[sb, sc] for sc in self._groups(C, L.PREP_MAX_CHANNELS)]
+            rows.append(parts[0] if len(parts) == 1 else torch.cat(parts, 1))
+        return rows[0] if len(rows) == 1 else torch.cat(rows)
+
+    def _low_res(self, lib, x, plan, own):
+        on = plan["lowres_on"]
+        if not on.any():
+            return x, own
+        if not own:
+            x, own = x.clone(), True
+        full = tuple(x.shape[2:])
+        for b, c in zip(*np.nonzero(on)):
+            small = ops_raw.zoom_nearest(lib, x[b, c:c + 1], plan["lowres_shape"][b, c].tolist())
+            x[b, c:c + 1] = ops_raw.zoom(lib, small, full, 3, True) if tuple(small.shape[1:]) != full else small
+        return x, own
+
+    # ---- per-sample ATen arithmetic, the parameters as device vectors built without a copy from the host ------------------------------
+    def _vec(self, values, like):
+        return torch.cat([torch.full((1,), float(v), dtype=like.dtype, device=like.device) for v in values]).view(-1, 1, 1, 1)
+
+    def _gamma(self, v, gam, invert):
+        """one sample (C, D, H, W), as DeviceAugmenter._gamma"""
+        v = -v if invert else v
+        red = (1, 2, 3)
+        mn, sd = v.mean(red, keepdim=True), v.std(red, keepdim=True)
+        lo = v.amin(red, keepdim=True)
+        rng = v.amax(red, keepdim=True) - lo
+        w = ((v - lo) / (rng + 1e-7)).clamp_min(0).pow(gam) * rng + lo
+        w = w - w.mean(red, keepdim=True)
+        w = w / (w.std(red, keepdim=True) + 1e-8) * sd + mn
+        return -w if invert else w
+
+    def __call__(self, image: torch.Tensor, label: torch.Tensor):
+        """image (B, C, D, H, W) float32, label (B, D, H, W) integer class map -> augmented copies (same shapes / dtypes)"""
+        if not L.on_device(image) or not L.on_device(label):
+            raise RuntimeError("SplineAugmenter runs on the HIP library's kernels (csrc/augment.hip): image and label must live on "
+                               "the GPU; on host tensors use DeviceAugmenter (augment=True)")
+        if image.dim() != 5 or label.dim() != 4 or image.dtype != torch.float32:
+            raise RuntimeError(f"SplineAugmenter: image (B, C, D, H, W) float32 and label (B, D, H, W) are required, got "
+                               f"{tuple(image.shape)} {image.dtype} and {tuple(label.shape)}")
+        lib = L.get_lib()
+        B, C = image.shape[:2]
+        plan = self.draw(B, C, tuple(image.shape[2:]))
+        x, y = image, label
+        if self.spatial:
+            x, y = self._spatial(lib, x, y, plan)
+        own = x is not image                           # whether x may be written in place
+        own_y = y is not label
+        for b in np.nonzero(plan["noise_on"])[0]:
+            if not own:
+                x, own = x.clone(), True
+            x[b] += torch.randn(x.shape[1:], device=x.device, generator=self.g, dtype=x.dtype) * float(plan["noise_scale"][b])
+        blurred = self._blur(lib, x, plan)
+        own, x = own or blurred is not x, blurred
+        for b in np.nonzero(plan["bright_on"])[0]:
+            if not own:
+                x, own = x.clone(), True
+            x[b] *= self._vec(plan["bright"][b], x)
+        for b in np.nonzero(plan["contrast_on"])[0]:
+            if not own:
+                x, own = x.clone(), True
+            v, red = x[b], (1, 2, 3)
+            mn, lo, hi = v.mean(red, keepdim=True), v.amin(red, keepdim=True), v.amax(red, keepdim=True)
+            x[b] = torch.minimum(torch.maximum((v - mn) * self._vec(plan["contrast"][b], x) + mn, lo), hi)
+        x, own = self._low_res(lib, x, plan, own)
+        for key, invert in (("gamma_inv", True), ("gamma", False)):
+            for b in np.nonzero(plan[key + "_on"])[0]:
+                if not own:
+                    x, own = x.clone(), True
+                x[b] = self._gamma(x[b], self._vec(plan[key][b], x), invert)
+        for b in range(B):
+            axes = [ax for j, ax in enumerate(self.mirror_axes) if plan["mirror"][b, j]]
+            if axes:
+                if not own:
+                    x, own = x.clone(), True
+                if not own_y:
+                    y, own_y = y.clone(), True
+                x[b] = x[b].flip([1 + ax for ax in axes])
+                y[b] = y[b].flip(axes)
+        return x.contiguous(), y.contiguous()
+
+
+def select_augmenter(augment):
+    """the class behind a feeder's truthy `augment` argument: "spline" -> SplineAugmenter, anything else (True) -> DeviceAugmenter"""
+    return SplineAugmenter if isinstance(augment, str) and augment == "spline" else DeviceAugmenter

@@ -30,6 +30,7 @@
 #include <string.h>
 
 #include "segm_device.h"
+#include "spline_common.h"
 
 namespace segm {
 
@@ -45,14 +46,8 @@ __device__ __forceinline__ void zoom_add_lds(int32_t* p, int32_t v) { __hip_atom
 __device__ __forceinline__ void zoom_add64(long long* p, long long v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 #endif
 
-constexpr double kPole = -0.26794919243112270647;                      // sqrt(3) - 2
-constexpr double kGain = (1.0 - kPole) * (1.0 - 1.0 / kPole);          // 6
-constexpr double kFir0 = kGain * (-kPole / (1.0 - kPole * kPole));     // sqrt(3)
 constexpr int kPad = 12;                // scipy's npad for mode 'nearest'
 constexpr int kMargin = 2;              // coefficients kept on either side of a line
-constexpr int kFirTaps = 32;
-constexpr int kInitTerms = 40;
-constexpr int kLineBatch = 8;
 constexpr int kZoomHeadBytes = 256;     // the front of the workspace: min keys [8], max keys [8]
 constexpr int kZoomMaxC = SEGM_PREP_MAX_CHANNELS;
 constexpr int kBinNeg = 256, kBinHigh = 257;

@@ -79,7 +79,7 @@ class PatchLoader:
     `j >= round(batch_size * (1 - oversample_foreground_percent))`, or with probability `oversample_foreground_percent` under
     `probabilistic_oversampling`; otherwise its box is uniform.  A case smaller than the patch is padded with zeros on both sides.
     All draws come from the global `np.random`, in the reference's order.  `seed` seeds the augmenter (`augment=True`: the batch of
-    `next()` goes through `augment.DeviceAugmenter`)."""
+    `next()` goes through `augment.DeviceAugmenter`; `augment="spline"`: through `augment.SplineAugmenter`)."""
 
     def __init__(self, dataset, patch_size, batch_size: int = 2, oversample_foreground_percent: float = 0.33,
                  probabilistic_oversampling: bool = False, device=None, augment: bool = False, seed: int = 42):
@@ -95,8 +95,8 @@ class PatchLoader:
         self.device = torch.device(device if device is not None else getattr(dataset, "device", "cpu"))
         self.augmenter = None
         if augment:
-            from .augment import DeviceAugmenter
-            self.augmenter = DeviceAugmenter(self.device, seed=seed)
+            from .augment import select_augmenter
+            self.augmenter = select_augmenter(augment)(self.device, seed=seed)
 
     def _oversample_last_XX_percent(self, sample_idx: int) -> bool:
         return not sample_idx < round(self.batch_size * (1 - self.oversample_foreground_percent))

@@ -301,6 +301,8 @@ EXPORTS = (
     "segm_ccl_select_workspace_bytes",
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
     "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
+    "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
+    "segm_gauss_blur",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -416,6 +418,51 @@ class ZoomLabelsArgs(C.Structure):
                 ("seg", C.c_void_p), ("out", C.c_void_p), ("counts", C.c_void_p), ("stream", C.c_void_p)]
 
 
+AUG_MAX_SAMPLES, AUG_MAX_VOLUMES, BLUR_MAX_RADIUS = 8, 64, 4                   # SEGM_AUG_MAX_SAMPLES / _VOLUMES, SEGM_BLUR_MAX_RADIUS
+
+
+class SplineCoefsArgs(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("reserved", C.c_int32),
+                ("stride_n", C.c_int64), ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("on", C.c_uint8 * AUG_MAX_SAMPLES),
+                ("data", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class AffineSpline3Args(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("reserved", C.c_int32),
+                ("stride_n", C.c_int64), ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("matrix", (C.c_double * 12) * AUG_MAX_SAMPLES),
+                ("cval", C.c_float), ("reserved2", C.c_int32),
+                ("on", C.c_uint8 * AUG_MAX_SAMPLES),
+                ("data", C.c_void_p), ("coefs", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class AffineLabelsArgs(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("wide", C.c_int32),
+                ("reserved", C.c_int32),
+                ("matrix", (C.c_double * 12) * AUG_MAX_SAMPLES),
+                ("on", C.c_uint8 * AUG_MAX_SAMPLES),
+                ("seg", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class ZoomNearestArgs(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("out_depth", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32), ("reserved", C.c_int32),
+                ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("data", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class GaussBlurArgs(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("reserved", C.c_int32),
+                ("stride_n", C.c_int64), ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("sigma", C.c_double * AUG_MAX_VOLUMES), ("on", C.c_uint8 * AUG_MAX_VOLUMES),
+                ("data", C.c_void_p), ("out", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
 def header_abi_version() -> int:
     """SEGM_ABI_VERSION as include/segmamba_hip.h declares it (what a freshly built library must report)"""
     import re
@@ -514,6 +561,12 @@ class SegmLib:
         sig("segm_zoom", [C.POINTER(ZoomArgs)], C.c_int)
         sig("segm_zoom_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_zoom_labels", [C.POINTER(ZoomLabelsArgs)], C.c_int)
+        sig("segm_spline_coefs", [C.POINTER(SplineCoefsArgs)], C.c_int)
+        sig("segm_spline_coefs_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
+        sig("segm_affine_spline3", [C.POINTER(AffineSpline3Args)], C.c_int)
+        sig("segm_affine_labels", [C.POINTER(AffineLabelsArgs)], C.c_int)
+        sig("segm_zoom_nearest", [C.POINTER(ZoomNearestArgs)], C.c_int)
+        sig("segm_gauss_blur", [C.POINTER(GaussBlurArgs)], C.c_int)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

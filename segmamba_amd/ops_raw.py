@@ -1808,6 +1808,146 @@ def zoom_labels(lib: L.SegmLib, seg: torch.Tensor, new_shape, want_counts: bool 
 
 
 # ---------------------------------------------------------------------------------------------------------
+# augmentation at the reference's interpolation orders (csrc/augment.hip): spline coefficients, the affine warp of data and
+# labels, order-0 zoom, gaussian blur.  Matrices, sigmas and flags are host values and travel in the argument structs.
+# ---------------------------------------------------------------------------------------------------------
+def _aug_batch(x, what: str):
+    """(N, C, D, H, W) fp32 with a unit stride along x, N <= 8, C <= 8: -> (N, C, D, H, W, stride_n, stride_c, stride_z, stride_y)"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise RuntimeError(f"{what}: a batch (N, C, D, H, W) is required, got {getattr(x, 'shape', type(x))}")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"{what}: float32 data are required, got {x.dtype}")
+    N, C_, D, H, W = x.shape
+    if not 1 <= N <= L.AUG_MAX_SAMPLES or not 1 <= C_ <= L.PREP_MAX_CHANNELS:
+        raise RuntimeError(f"{what}: 1 .. {L.AUG_MAX_SAMPLES} samples and 1 .. {L.PREP_MAX_CHANNELS} channels per call, got {tuple(x.shape)}")
+    _zoom_shape((D, H, W), what)
+    sn, sc, sz, sy, sx = x.stride()
+    if W > 1 and sx != 1:
+        raise RuntimeError(f"{what}: data need a unit stride along the last dimension")
+    if (H > 1 and sy < W) or min(sn, sc, sz) < 0:
+        raise RuntimeError(f"{what}: unsupported data strides {x.stride()}")
+    return N, C_, D, H, W, sn, sc, sz, max(sy, W)
+
+
+def _aug_flags(on, n: int, what: str):
+    on = [True] * n if on is None else [bool(v) for v in on]
+    if len(on) != n:
+        raise RuntimeError(f"{what}: {n} on / off flags are required, got {len(on)}")
+    return on
+
+
+def _aug_matrices(a, matrices, n: int, what: str) -> None:
+    import numpy as np
+    m = np.asarray(matrices, dtype=np.float64)
+    if m.shape != (n, 3, 4) or not np.isfinite(m).all():
+        raise RuntimeError(f"{what}: finite matrices ({n}, 3, 4) [A | t] are required, got shape {m.shape}")
+    for b in range(n):
+        a.matrix[b][:] = m[b].reshape(12).tolist()
+
+
+def spline_coefs(lib: L.SegmLib, x: torch.Tensor, on=None) -> torch.Tensor:
+    """x (N, C, D, H, W) fp32, N <= 8, C <= 8 -> float64 (N, C, D, H, W): `scipy.ndimage.spline_filter(x, 3, output=float64,
+    mode='mirror')` of every volume of the samples that are `on` (default: all); the volumes of the others are left unwritten."""
+    N, C_, D, H, W, sn, sc, sz, sy = _aug_batch(x, "spline_coefs")
+    on = _aug_flags(on, N, "spline_coefs")
+    nbytes = lib.dll.segm_spline_coefs_workspace_bytes(N, C_, D, H, W)
+    if nbytes == 0:
+        raise RuntimeError(f"spline_coefs: no workspace size for {tuple(x.shape)}")
+    coefs = torch.empty((N, C_, D, H, W), dtype=torch.float64, device=x.device)
+    a = L.SplineCoefsArgs()
+    a.samples, a.channels, a.depth, a.height, a.width = N, C_, D, H, W
+    a.stride_n, a.stride_c, a.stride_z, a.stride_y = sn, sc, sz, sy
+    a.on[:N] = [int(v) for v in on]
+    a.data, a.workspace, a.workspace_bytes, a.stream = x.data_ptr(), coefs.data_ptr(), nbytes, L.stream_handle(x)
+    lib.check(lib.dll.segm_spline_coefs(a), "spline_coefs")
+    return coefs
+
+
+def affine_spline3(lib: L.SegmLib, x: torch.Tensor, coefs: torch.Tensor, matrices, on=None, cval: float = 0.0) -> torch.Tensor:
+    """x (N, C, D, H, W) fp32 and its `spline_coefs` -> (N, C, D, H, W) fp32: sample n at p = A_n (z, y, x)^T + t_n, matrices (N, 3, 4)
+    = [A | t] host float64 - `map_coordinates(x.astype(float64), p, order=3, mode='constant', cval).astype(float32)`.  Samples that
+    are off are copied bit for bit."""
+    N, C_, D, H, W, sn, sc, sz, sy = _aug_batch(x, "affine_spline3")
+    on = _aug_flags(on, N, "affine_spline3")
+    _same_volume(coefs, "affine_spline3: coefs", torch.float64, tuple(x.shape), x.device)
+    out = torch.empty((N, C_, D, H, W), dtype=torch.float32, device=x.device)
+    a = L.AffineSpline3Args()
+    a.samples, a.channels, a.depth, a.height, a.width = N, C_, D, H, W
+    a.stride_n, a.stride_c, a.stride_z, a.stride_y = sn, sc, sz, sy
+    _aug_matrices(a, matrices, N, "affine_spline3")
+    a.cval = float(cval)
+    a.on[:N] = [int(v) for v in on]
+    a.data, a.coefs, a.out, a.stream = x.data_ptr(), coefs.data_ptr(), out.data_ptr(), L.stream_handle(x)
+    lib.check(lib.dll.segm_affine_spline3(a), "affine_spline3")
+    return out
+
+
+def affine_labels(lib: L.SegmLib, seg: torch.Tensor, matrices, on=None) -> torch.Tensor:
+    """seg (N, D, H, W) int16 or int64, contiguous, N <= 8 -> the same shape and dtype: 0 outside the volume, inside the largest
+    label whose trilinear weight at p is >= 0.5, else 0 (batchgenerators' `interpolate_img(is_seg=True, order=1, cval=-1)`).
+    Samples that are off are copied."""
+    if not isinstance(seg, torch.Tensor) or seg.dim() != 4:
+        raise RuntimeError(f"affine_labels: a (N, D, H, W) seg is required, got {getattr(seg, 'shape', type(seg))}")
+    if seg.dtype not in (torch.int16, torch.int64):
+        raise RuntimeError(f"affine_labels: an int16 or int64 seg is required, got {seg.dtype}")
+    if not seg.is_contiguous():
+        raise RuntimeError("affine_labels: seg must be contiguous")
+    N, D, H, W = seg.shape
+    if not 1 <= N <= L.AUG_MAX_SAMPLES:
+        raise RuntimeError(f"affine_labels: 1 .. {L.AUG_MAX_SAMPLES} samples per call, got {N}")
+    _zoom_shape((D, H, W), "affine_labels")
+    on = _aug_flags(on, N, "affine_labels")
+    out = torch.empty_like(seg)
+    a = L.AffineLabelsArgs()
+    a.samples, a.depth, a.height, a.width, a.wide = N, D, H, W, 1 if seg.dtype == torch.int64 else 0
+    _aug_matrices(a, matrices, N, "affine_labels")
+    a.on[:N] = [int(v) for v in on]
+    a.seg, a.out, a.stream = seg.data_ptr(), out.data_ptr(), L.stream_handle(seg)
+    lib.check(lib.dll.segm_affine_labels(a), "affine_labels")
+    return out
+
+
+def zoom_nearest(lib: L.SegmLib, data: torch.Tensor, new_shape) -> torch.Tensor:
+    """data (C, D, H, W) fp32 with a unit stride along x, C <= 8 -> (C,) + new_shape: `scipy.ndimage.zoom(order=0, mode='nearest',
+    grid_mode=True)` per channel (skimage's `resize(order=0, mode='edge', anti_aliasing=False)`)."""
+    C_, D, H, W, sc, sz, sy = _prep_data(data, "zoom_nearest")
+    _zoom_shape((D, H, W), "zoom_nearest: data")
+    new_shape = _zoom_shape(new_shape, "zoom_nearest")
+    out = torch.empty((C_,) + new_shape, dtype=torch.float32, device=data.device)
+    a = L.ZoomNearestArgs()
+    a.channels, a.depth, a.height, a.width = C_, D, H, W
+    a.out_depth, a.out_height, a.out_width = new_shape
+    a.stride_c, a.stride_z, a.stride_y = sc, sz, sy
+    a.data, a.out, a.stream = data.data_ptr(), out.data_ptr(), L.stream_handle(data)
+    lib.check(lib.dll.segm_zoom_nearest(a), "zoom_nearest")
+    return out
+
+
+def gauss_blur(lib: L.SegmLib, x: torch.Tensor, sigma, on=None) -> torch.Tensor:
+    """x (N, C, D, H, W) fp32, N <= 8, C <= 8; sigma and on: N * C host values, volume n * C + c -> (N, C, D, H, W) fp32:
+    `scipy.ndimage.gaussian_filter(x[n, c], sigma)` (truncate 4, mode 'reflect', fp32 between the passes) for the volumes that are
+    on, a copy of the others.  int(4 sigma + 0.5) must not exceed 4."""
+    N, C_, D, H, W, sn, sc, sz, sy = _aug_batch(x, "gauss_blur")
+    on = _aug_flags(on, N * C_, "gauss_blur")
+    sigma = [float(v) for v in sigma]
+    if len(sigma) != N * C_:
+        raise RuntimeError(f"gauss_blur: {N * C_} sigmas are required, got {len(sigma)}")
+    if any(f and not (s > 0.0 and int(4.0 * s + 0.5) <= L.BLUR_MAX_RADIUS) for s, f in zip(sigma, on)):
+        raise RuntimeError(f"gauss_blur: every sigma must be positive with a radius int(4 sigma + 0.5) <= {L.BLUR_MAX_RADIUS}, got {sigma}")
+    out = torch.empty((N, C_, D, H, W), dtype=torch.float32, device=x.device)
+    ws = torch.empty_like(out) if any(on) else None
+    a = L.GaussBlurArgs()
+    a.samples, a.channels, a.depth, a.height, a.width = N, C_, D, H, W
+    a.stride_n, a.stride_c, a.stride_z, a.stride_y = sn, sc, sz, sy
+    a.sigma[:N * C_] = sigma
+    a.on[:N * C_] = [int(v) for v in on]
+    a.data, a.out, a.stream = x.data_ptr(), out.data_ptr(), L.stream_handle(x)
+    a.workspace, a.workspace_bytes = L.fptr(ws), 0 if ws is None else ws.numel() * 4
+    lib.check(lib.dll.segm_gauss_blur(a), "gauss_blur")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -1851,5 +1991,6 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
               "space_to_depth2", "seg_regions", "edt_sq", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
-              "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels"):
+              "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "spline_coefs", "affine_spline3", "affine_labels",
+              "zoom_nearest", "gauss_blur"):
     globals()[_name] = _device_guard(globals()[_name])

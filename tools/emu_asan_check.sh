@@ -116,5 +116,18 @@ for shp, new in (((5, 1, 9), (7, 3, 18)), ((3, 4, 300), (2, 6, 150)), ((6, 7, 8)
     sz = torch.randint(-1, 4, shp, generator=g).to(torch.int16)
     ops_raw.zoom_labels(emu, sz, new); ops_raw.zoom_labels(emu, sz, new, want_counts=False)
 print("zoom / zoom_labels ok", flush=True)
+# augmentation: sides shorter than every filter support, a side of 1, two row tiles of the x prefilter, strided views, mixed flags
+import numpy as np
+from segmamba_amd.augment import SplineAugmenter
+for shp in ((5, 2, 300), (6, 1, 9), (7, 9, 8)):
+    xa = torch.randn(3, 4, shp[0], shp[1], shp[2] + 5, generator=g)[:, ::2, :, :, 2:-3]
+    ma = np.stack([SplineAugmenter.matrix(a, s, shp) for a, s in (((0.3, -0.2, 0.45), 0.85), ((0.0, 0.0, 0.0), 0.7), ((-0.52, 0.52, 0.1), 1.35))])
+    on = [True, False, True]
+    ops_raw.affine_spline3(emu, xa, ops_raw.spline_coefs(emu, xa, on), ma, on)
+    for dt in (torch.int16, torch.int64):
+        ops_raw.affine_labels(emu, torch.randint(0, 4, (3,) + shp, generator=g).to(dt), ma, on)
+    ops_raw.gauss_blur(emu, xa, [0.5, 0.63, 0.88, 1.0, 0.7, 0.9], [True, True, False, True, True, True])
+    ops_raw.zoom_nearest(emu, xa[0], (3, 4, 7)); ops_raw.zoom_nearest(emu, xa[1], (9, 1, 400))
+print("spline_coefs / affine_spline3 / affine_labels / gauss_blur / zoom_nearest ok", flush=True)
 print("AddressSanitizer run finished without reports")
 PY
