@@ -883,6 +883,58 @@ typedef struct segm_border_distances_args {
 size_t segm_border_distances_workspace_bytes(int64_t voxels, int32_t n_items);
 int segm_border_distances(const segm_border_distances_args* args);
 
+/* The same transform for sides up to SEGM_EDT_LONG_MAX_LINE, at a cost linear in the line length (additive to ABI 10;
+ * csrc/edt_long.hip).  Meaning, planes, spacing rules and sentinels are those of segm_edt_sq, and the struct has its layout up to
+ * `stream` with `reserved` taken by max_workgroups; segm_edt_sq itself keeps its limit and its refusals.
+ * x pass: the row's bit planes as 64-bit masks in LDS, clz / ctz per lane.  y and z pass: the lower envelope of the parabolas
+ * g[i] + (s (u - i))^2 (Meijster / Felzenszwalb-Huttenlocher), one thread per line, a forward scan that stacks (position, start of its
+ * interval, g) and a backward scan that writes - in place in `out`.  The stacks live in the workspace, 8 bytes x line length per
+ * thread in flight: workgroups are persistent and reuse their area for one batch of 256 lines after the other, so the size follows
+ * the grid, not the volume (1 GiB at 400 x 512 x 512, reached by any volume with at least 1024 batches of 512-long lines).
+ * max_workgroups: 0 = the default (1024); a smaller positive value lowers the grid of the line passes (larger ones change nothing).
+ * fp32 = 0: integer arithmetic, equal to segm_edt_sq at every voxel.  fp32 = 1: intersections in fp64, values in fp32 rounded as
+ * segm_edt_sq rounds them - within its 1e-6 relative bound of the exact value, not bit-equal to it (the two may pick different
+ * minimisers among candidates that differ by a rounding).  Deterministic: no atomics, two calls are bit-equal.
+ * depth, height, width in [1, SEGM_EDT_LONG_MAX_LINE], depth * height * width <= SEGM_METRICS_MAX_VOXELS (else SEGM_E_SHAPE);
+ * workspace NULL, misaligned (8 bytes) or smaller than segm_edt_sq_long_workspace_bytes: SEGM_E_WORKSPACE. */
+#define SEGM_EDT_LONG_MAX_LINE 2048
+typedef struct segm_edt_sq_long_args {
+    int32_t depth, height, width;
+    int32_t n_volumes, n_planes, fp32;
+    float spacing_z, spacing_y, spacing_x;
+    int32_t max_workgroups;        /* 0 = default */
+    int32_t plane_volume[SEGM_METRICS_MAX_PLANES];
+    int32_t plane_bit[SEGM_METRICS_MAX_PLANES];
+    const uint8_t* volumes;        /* (n_volumes, depth, height, width) */
+    void* out;                     /* (n_planes, depth, height, width) int32 or fp32 */
+    void* stream;
+    void* workspace;     size_t workspace_bytes;
+} segm_edt_sq_long_args;
+size_t segm_edt_sq_long_workspace_bytes(int32_t depth, int32_t height, int32_t width, int32_t n_planes, int32_t fp32);
+int segm_edt_sq_long(const segm_edt_sq_long_args* args);
+
+/* Bounding boxes of bit planes in one pass over the volumes.  Item i: the voxels whose bit item_bit[i] is set in volume
+ * item_volume[i], OR-ed with bit item_bit2[i] of volume item_volume2[i] unless that is -1 (the border of a prediction and the border
+ * of a ground truth: every border voxel of either lies in the box, so the nearest one does too, and the distance transform may
+ * run on the crop).
+ *   boxes[6 i ..] = z0, z1, y0, y1, x0, x1, half-open; an item without a set voxel leaves z1 = y1 = x1 = 0 (and the lower ends at
+ *   0x7f7f7f7f), as segm_nonzero_mask_bbox marks an empty mask.  All SEGM_METRICS_MAX_PLANES x 6 values are OVERWRITTEN.
+ * 16-byte loads along x when width % 16 == 0; a wave that saw no set bit of an item exchanges nothing for it; per workgroup at
+ * most 6 integer min / max atomics per item, whose order does not matter: deterministic.
+ * Sides below 2^20, depth * height * width <= SEGM_METRICS_MAX_VOXELS, n_volumes and n_items in [1, SEGM_METRICS_MAX_PLANES]. */
+typedef struct segm_planes_bbox_args {
+    int32_t depth, height, width;
+    int32_t n_volumes, n_items, reserved;
+    int32_t item_volume[SEGM_METRICS_MAX_PLANES];
+    int32_t item_bit[SEGM_METRICS_MAX_PLANES];
+    int32_t item_volume2[SEGM_METRICS_MAX_PLANES];     /* -1: a single plane */
+    int32_t item_bit2[SEGM_METRICS_MAX_PLANES];
+    const uint8_t* volumes;        /* (n_volumes, depth, height, width) */
+    int32_t* boxes;                /* SEGM_METRICS_MAX_PLANES x 6 int32 in device memory */
+    void* stream;
+} segm_planes_bbox_args;
+int segm_planes_bbox(const segm_planes_bbox_args* args);
+
 /* ------------------------------------------------------------------------------------------------
  * Finishing a prediction on the device (additive to ABI 10; csrc/postprocess.hip).
  * Replaces, of the reference's light_training/prediction.py: predict_raw_probability (:33-62) + the argmax of 4_predict.py:81 +

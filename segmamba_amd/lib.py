@@ -297,6 +297,7 @@ EXPORTS = (
     "segm_stem_conv_wgrad", "segm_stem_conv_wgrad_workspace_bytes", "segm_stem_conv_wgrad_workspace_bytes2", "segm_wgrad_gemm", "segm_wgrad_gemm_workspace_bytes",
     "segm_skinny_tn", "segm_skinny_tn_workspace_bytes", "segm_channel_sum", "segm_channel_sum_workspace_bytes", "segm_selective_scan_regular_shape",
     "segm_seg_regions", "segm_seg_regions_workspace_bytes", "segm_edt_sq", "segm_border_distances", "segm_border_distances_workspace_bytes",
+    "segm_edt_sq_long", "segm_edt_sq_long_workspace_bytes", "segm_planes_bbox",
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
@@ -334,6 +335,26 @@ class EdtSqArgs(C.Structure):
                 ("spacing_z", C.c_float), ("spacing_y", C.c_float), ("spacing_x", C.c_float), ("reserved", C.c_int32),
                 ("plane_volume", C.c_int32 * METRICS_MAX_PLANES), ("plane_bit", C.c_int32 * METRICS_MAX_PLANES),
                 ("volumes", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p)]
+
+
+EDT_LONG_MAX_LINE = 2048                                                       # SEGM_EDT_LONG_MAX_LINE
+
+
+class EdtSqLongArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("n_volumes", C.c_int32), ("n_planes", C.c_int32), ("fp32", C.c_int32),
+                ("spacing_z", C.c_float), ("spacing_y", C.c_float), ("spacing_x", C.c_float), ("max_workgroups", C.c_int32),
+                ("plane_volume", C.c_int32 * METRICS_MAX_PLANES), ("plane_bit", C.c_int32 * METRICS_MAX_PLANES),
+                ("volumes", C.c_void_p), ("out", C.c_void_p), ("stream", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
+
+
+class PlanesBboxArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("n_volumes", C.c_int32), ("n_items", C.c_int32), ("reserved", C.c_int32),
+                ("item_volume", C.c_int32 * METRICS_MAX_PLANES), ("item_bit", C.c_int32 * METRICS_MAX_PLANES),
+                ("item_volume2", C.c_int32 * METRICS_MAX_PLANES), ("item_bit2", C.c_int32 * METRICS_MAX_PLANES),
+                ("volumes", C.c_void_p), ("boxes", C.c_void_p), ("stream", C.c_void_p)]
 
 
 class BorderDistancesArgs(C.Structure):
@@ -548,6 +569,9 @@ class SegmLib:
         sig("segm_edt_sq", [C.POINTER(EdtSqArgs)], C.c_int)
         sig("segm_border_distances", [C.POINTER(BorderDistancesArgs)], C.c_int)
         sig("segm_border_distances_workspace_bytes", [C.c_int64, C.c_int32], C.c_size_t)
+        sig("segm_edt_sq_long", [C.POINTER(EdtSqLongArgs)], C.c_int)
+        sig("segm_edt_sq_long_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
+        sig("segm_planes_bbox", [C.POINTER(PlanesBboxArgs)], C.c_int)
         sig("segm_resample_argmax", [C.POINTER(ResampleArgmaxArgs)], C.c_int)
         sig("segm_ccl_roots", [C.POINTER(CclRootsArgs)], C.c_int)
         sig("segm_ccl_roots_workspace_bytes", [C.c_int64], C.c_size_t)

@@ -5,10 +5,17 @@ the host; `3_train.py:82-119` computes a validation Dice the same way.  The func
 (connectivity 1, `numpy.percentile` interpolation) and run on the library's kernels: one pass for region counts and borders, one
 batched exact squared distance transform, one gather of the distances at the border voxels.  Tensors stay on the device; numpy
 arrays and host tensors are uploaded.  Only a handful of scalars is read back per call.
+
+Volumes with a side beyond 256 (CT cases) take the box route: one launch gives the box of `border(P) | border(G)` of every region,
+both border volumes are cropped to it, and the crop is transformed by the brute-force kernel if its sides are at most 256, else by
+the linear-time one (csrc/edt_long.hip, sides up to 2048).  The crop is exact: every border voxel of either mask lies inside the
+box, so the nearest one does too.  `SEGM_EDT_LONG=1` (read per call) forces the box route and the linear-time kernel at every
+size, `SEGM_EDT_LONG=box` the box route with the kernel chosen by the crop's size, i.e. what a large volume gets.
 """
 from __future__ import annotations
 
 import math
+import os
 from typing import Iterable, Optional, Sequence, Tuple
 
 import numpy as np
@@ -22,6 +29,28 @@ _BINARY = ((1,),)
 _INT_SENTINEL = 2 ** 31 - 1
 
 _tables = {}
+
+
+def _long_mode() -> str:
+    """SEGM_EDT_LONG, read per call: "" (route by size), "1" (box route, linear-time kernel) or "box" (box route, kernel by crop size)"""
+    v = os.environ.get("SEGM_EDT_LONG", "").strip().lower()
+    if v in ("", "0"):
+        return ""
+    if v not in ("1", "box"):
+        raise RuntimeError(f"SEGM_EDT_LONG must be unset, 0, 1 or box, got {v!r}")
+    return v
+
+
+def _readback(t: torch.Tensor) -> list:
+    """a device-to-host copy of a few scalars (the only kind this module makes: two per case)"""
+    return t.tolist()
+
+
+def _edt_sq(lib, volumes: torch.Tensor, planes, spacing, mode: str) -> torch.Tensor:
+    """the brute-force kernel when every side is at most 256 (and the linear-time one is not forced), else the linear-time kernel"""
+    if mode != "1" and max(volumes.shape[1:]) <= L.EDT_MAX_LINE:
+        return ops_raw.edt_sq(lib, volumes, planes, spacing)
+    return ops_raw.edt_sq_long(lib, volumes, planes, spacing)
 
 
 def _table(regions, device) -> torch.Tensor:
@@ -100,10 +129,11 @@ def dc(result, reference) -> float:
 
 def distance_transform_edt(mask, sampling: Optional[Sequence[float]] = None) -> torch.Tensor:
     """scipy.ndimage.distance_transform_edt: the distance of every non-zero voxel to the nearest zero voxel (0 at zero voxels), fp32;
-    +inf everywhere when `mask` has no zero voxel.  Each side of the volume is limited to 256 voxels."""
+    +inf everywhere when `mask` has no zero voxel.  Each side of the volume is limited to 2048 voxels (RuntimeError beyond): the
+    brute-force kernel serves volumes whose sides are all at most 256, the linear-time kernel every larger one."""
     m = _volume3(_to_device(mask), "distance_transform_edt")
     zero = (m == 0).to(torch.uint8).contiguous()
-    e = ops_raw.edt_sq(L.get_lib(), zero[None], [(0, 0)], sampling)[0]
+    e = _edt_sq(L.get_lib(), zero[None], [(0, 0)], sampling, _long_mode())[0]
     if e.dtype == torch.int32:
         return torch.where(e == _INT_SENTINEL, torch.full((), math.inf, device=e.device), e.float().sqrt())
     return e.sqrt()
@@ -116,7 +146,17 @@ class _Pass:
         self.lib = L.get_lib()
         self.n_regions = len(regions)
         self.borders, counts = ops_raw.seg_regions(self.lib, pred, gt, _table(regions, pred.device))
-        self.counts = counts[:, :self.n_regions].tolist()                 # first readback: [|P|, |G|, |P and G|, |dP|, |dG|][region]
+        self.mode = _long_mode()
+        self.boxed = self.mode != "" or max(pred.shape) > L.EDT_MAX_LINE
+        if not self.boxed:
+            self.counts = counts[:, :self.n_regions].tolist()             # first readback: [|P|, |G|, |P and G|, |dP|, |dG|][region]
+            return
+        # the boxes of border(P) | border(G) of every region, issued before the first readback and read back with the counts
+        boxes = ops_raw.planes_bbox(self.lib, self.borders, [(0, r, 1, r) for r in range(self.n_regions)])
+        flat = _readback(torch.cat([counts.reshape(-1), boxes[:self.n_regions].reshape(-1).to(torch.int64)]))
+        w = L.METRICS_MAX_REGIONS
+        self.counts = [flat[q * w:q * w + self.n_regions] for q in range(5)]
+        self.boxes = [flat[5 * w + 6 * r:5 * w + 6 * r + 6] for r in range(self.n_regions)]
 
     def live(self, r: int) -> bool:
         return self.counts[0][r] > 0 and self.counts[1][r] > 0
@@ -127,6 +167,8 @@ class _Pass:
     def distances(self, regions_idx, spacing):
         """-> (flat fp32 vector, [(offset, n(border P), n(border G))] per region of `regions_idx`): for each region the distances from
         the border of P to the border of G, then from the border of G to the border of P"""
+        if self.boxed:
+            return self._distances_boxed(regions_idx, spacing)
         planes, items, cnt, seg = [], [], [], []
         off = 0
         for i, r in enumerate(regions_idx):
@@ -138,6 +180,24 @@ class _Pass:
             off += n_p + n_g
         edt = ops_raw.edt_sq(self.lib, self.borders, planes, spacing)
         return ops_raw.border_distances(self.lib, self.borders, edt, items, cnt), seg
+
+    def _distances_boxed(self, regions_idx, spacing):
+        """the same vector and segments from per-region crops to the box of border(P) | border(G): cropping keeps the memory order of
+        the border voxels and every candidate for the nearest one"""
+        parts, seg = [], []
+        off = 0
+        for r in regions_idx:
+            z0, z1, y0, y1, x0, x1 = self.boxes[r]
+            n_p, n_g = self.counts[3][r], self.counts[4][r]
+            if n_p + n_g > 0:
+                crop = self.borders[:, z0:z1, y0:y1, x0:x1].contiguous()
+                edt = _edt_sq(self.lib, crop, [(0, r), (1, r)], spacing, self.mode)      # plane 0: to the border of P; 1: of G
+                parts.append(ops_raw.border_distances(self.lib, crop, edt, [(0, r, 1), (1, r, 0)], [n_p, n_g]))
+            seg.append((off, n_p, n_g))
+            off += n_p + n_g
+        if not parts:
+            return torch.empty(0, dtype=torch.float32, device=self.borders.device), seg
+        return (parts[0] if len(parts) == 1 else torch.cat(parts)), seg
 
     def hausdorff(self, regions_idx, spacing):
         """-> [(hd95, hd)] per region of `regions_idx`, with one readback for all of them"""
@@ -152,8 +212,12 @@ class _Pass:
             lo = int(math.floor(rank))
             hi = min(lo + 1, n - 1)
             frac.append(rank - lo)
-            picks.append(s[[lo, hi, n - 1]])
-        vals = torch.stack(picks).double().cpu().numpy()                  # second readback
+            # the box route selects with host integers: no index tensor is uploaded, nothing but the two readbacks synchronises
+            picks.append(torch.stack((s[lo], s[hi], s[n - 1])) if self.boxed else s[[lo, hi, n - 1]])
+        if self.boxed:
+            vals = np.asarray(_readback(torch.stack(picks).double()))     # second readback
+        else:
+            vals = torch.stack(picks).double().cpu().numpy()              # second readback
         return [(float(v[0] + (v[1] - v[0]) * f), float(v[2])) for v, f in zip(vals, frac)]
 
 

@@ -1383,7 +1383,7 @@ def wgrad_gemm(lib: L.SegmLib, a: torch.Tensor, b: torch.Tensor, layout: int) ->
 
 
 # ---------------------------------------------------------------------------------------------------------
-# evaluation (csrc/metrics.hip): region counts and borders, squared distance transform, border distances
+# evaluation (csrc/metrics.hip, csrc/edt_long.hip): region counts and borders, squared distance transform, boxes, border distances
 # ---------------------------------------------------------------------------------------------------------
 def _label_volume(t: torch.Tensor, what: str, dims=(3,)) -> None:
     if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
@@ -1466,6 +1466,63 @@ def edt_sq(lib: L.SegmLib, volumes: torch.Tensor, planes, spacing=None) -> torch
     a.volumes, a.out, a.stream = volumes.data_ptr(), out.data_ptr(), L.stream_handle(volumes)
     lib.check(lib.dll.segm_edt_sq(a), "edt_sq")
     return out
+
+
+def edt_sq_long(lib: L.SegmLib, volumes: torch.Tensor, planes, spacing=None, max_workgroups: int = 0) -> torch.Tensor:
+    """`edt_sq` for sides up to 2048 (segm_edt_sq_long: linear in the line length, stacks in a workspace sized by the grid).  Same
+    arguments and result; int32 values equal `edt_sq`'s, fp32 values lie within the same 1e-6 relative bound.  max_workgroups: 0 = the
+    default, a smaller positive value lowers the grid of the line passes (a workgroup then reuses its stack area more often)."""
+    _label_volume(volumes, "edt_sq_long: volumes", dims=(4,))
+    V, D, H, W = volumes.shape
+    if max(D, H, W) > L.EDT_LONG_MAX_LINE:
+        raise RuntimeError(f"edt_sq_long: depth, height and width are limited to {L.EDT_LONG_MAX_LINE} (SEGM_E_SHAPE), got {(D, H, W)}")
+    if V > L.METRICS_MAX_PLANES:
+        raise RuntimeError(f"edt_sq_long: at most {L.METRICS_MAX_PLANES} volumes per call, got {V}")
+    planes = _plane_list(planes, V, "edt_sq_long")
+    max_workgroups = int(max_workgroups)
+    if max_workgroups < 0:
+        raise RuntimeError(f"edt_sq_long: max_workgroups must be 0 (default) or positive, got {max_workgroups}")
+    sp = _spacing3(spacing)
+    unit = _unit_spacing(spacing)
+    out = torch.empty(len(planes), D, H, W, dtype=torch.int32 if unit else torch.float32, device=volumes.device)
+    nbytes = lib.dll.segm_edt_sq_long_workspace_bytes(D, H, W, len(planes), 0 if unit else 1)
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=volumes.device)
+    a = L.EdtSqLongArgs()
+    a.depth, a.height, a.width, a.n_volumes, a.n_planes, a.fp32 = D, H, W, V, len(planes), 0 if unit else 1
+    a.spacing_z, a.spacing_y, a.spacing_x = sp
+    a.max_workgroups = max_workgroups
+    for i, (v, b) in enumerate(planes):
+        a.plane_volume[i], a.plane_bit[i] = v, b
+    a.volumes, a.out, a.stream = volumes.data_ptr(), out.data_ptr(), L.stream_handle(volumes)
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    lib.check(lib.dll.segm_edt_sq_long(a), "edt_sq_long")
+    return out
+
+
+def planes_bbox(lib: L.SegmLib, volumes: torch.Tensor, items) -> torch.Tensor:
+    """Bounding boxes of bit planes in one pass.  volumes (V, D, H, W) uint8; items: (volume, bit) or (volume, bit, volume2, bit2),
+    the latter the OR of two planes.  -> (16, 6) int32 on the device, row i = [z0, z1, y0, y1, x0, x1] of item i, half-open;
+    z1 = y1 = x1 = 0 for an item without a set voxel (and for the rows past the last item)."""
+    _label_volume(volumes, "planes_bbox: volumes", dims=(4,))
+    V, D, H, W = volumes.shape
+    if V > L.METRICS_MAX_PLANES:
+        raise RuntimeError(f"planes_bbox: at most {L.METRICS_MAX_PLANES} volumes per call, got {V}")
+    if max(D, H, W) >= 1 << 20:
+        raise RuntimeError(f"planes_bbox: sides are limited to 2^20 - 1, got {(D, H, W)}")
+    items = [tuple(int(v) for v in it) for it in items]
+    if any(len(it) not in (2, 4) for it in items):
+        raise RuntimeError("planes_bbox: an item is (volume, bit) or (volume, bit, volume2, bit2)")
+    _plane_list([it[:2] for it in items], V, "planes_bbox")
+    _plane_list([it[2:] for it in items if len(it) == 4] or [(0, 0)], V, "planes_bbox")
+    boxes = torch.empty(L.METRICS_MAX_PLANES, 6, dtype=torch.int32, device=volumes.device)
+    a = L.PlanesBboxArgs()
+    a.depth, a.height, a.width, a.n_volumes, a.n_items = D, H, W, V, len(items)
+    for i, it in enumerate(items):
+        a.item_volume[i], a.item_bit[i] = it[:2]
+        a.item_volume2[i], a.item_bit2[i] = it[2:] if len(it) == 4 else (-1, 0)
+    a.volumes, a.boxes, a.stream = volumes.data_ptr(), boxes.data_ptr(), L.stream_handle(volumes)
+    lib.check(lib.dll.segm_planes_bbox(a), "planes_bbox")
+    return boxes
 
 
 def border_distances(lib: L.SegmLib, borders: torch.Tensor, edt: torch.Tensor, items, counts) -> torch.Tensor:
@@ -1990,7 +2047,7 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "instnorm_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
-              "space_to_depth2", "seg_regions", "edt_sq", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
+              "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
               "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "spline_coefs", "affine_spline3", "affine_labels",
               "zoom_nearest", "gauss_blur"):
     globals()[_name] = _device_guard(globals()[_name])

@@ -6,7 +6,10 @@ form of the reference's 5_compute_metrics.py.
 Cases are the files of --pred that have a file of the same name in --gt.  Label volumes are read from .npy and .npz (the first
 array, or the one called "labels" / "seg" / "arr_0"); .nii / .nii.gz through nibabel or SimpleITK where one is installed, else through
 segmamba_amd.nifti.read_nifti (single-file NIfTI-1 as tools/finish_predictions.py and Predictor.save_to_nii write it).  Prints the
-per-case array, then its mean and standard deviation over the cases, and saves the (cases, regions, 2) array to --out."""
+per-case array, then its mean and standard deviation over the cases, and saves the (cases, regions, 2) array to --out.
+
+Volumes may measure up to 2048 voxels per side (CT cases of 512 x 512 x several hundred included): a volume with a side beyond 256 is
+scored on the crops to each region's border box, by the linear-time distance transform where a crop is still longer than 256."""
 import argparse
 import os
 import sys
@@ -53,7 +56,7 @@ def case_files(pred_dir: str, gt_dir: str):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0] + "  " + __doc__.split("\n\n")[-1].replace("\n", " "))
     ap.add_argument("--pred", required=True)
     ap.add_argument("--gt", required=True)
     ap.add_argument("--out")
