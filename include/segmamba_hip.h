@@ -407,6 +407,12 @@ size_t segm_conv3d_k3_cube_wgrad_workspace_bytes(int32_t batch, int32_t cin, int
  * act: 0 none, 1 ReLU, 2 LeakyReLU(slope).
  * Backward: `y` (the forward's output) is required iff act != 0 and a residual was added (the activation mask is then
  * not recomputable from x); pass NULL otherwise.  dresidual (NULL = not wanted) receives dy * act'(.).
+ * Two stated deviations (held per element against a float64 restatement by tests/norm_ref.py, tests/norm_checks.py):
+ *  - when dresidual is wanted, the type has 16 bits and act is LeakyReLU, g = dy * act'(.) is parked in dresidual ROUNDED to the
+ *    type by the statistics pass and dx is formed from that rounded value: dx is rounded twice, rstd * ulp(g) / 2 on top of its own
+ *    final rounding (it saves one read of y and of dy).  fp32, ReLU and calls without dresidual are not affected.
+ *  - the statistics are fp32 sums of x and x^2: their error grows with the condition number 1 + r^2 of E[x^2] - mean^2,
+ *    r = |mean| / std:  |mean' - mean| rstd <= 2^-16 (1 + r),  |rstd' / rstd - 1| <= 2^-15 (1 + r^2)  (3e-4 at r = 3, 2.7e-2 at r = 30).
  * ------------------------------------------------------------------------------------------------ */
 typedef struct segm_instnorm_fwd_args {
     int32_t instances, dtype, act, reserved;
@@ -440,7 +446,7 @@ typedef struct segm_instnorm_bwd_args {
     const float* mean;
     const float* rstd;
     void* dx;
-    void* dresidual;          /* or NULL */
+    void* dresidual;          /* or NULL.  16-bit + LeakyReLU: also the staging buffer of g, dx is then rounded twice (see above) */
     void* workspace;
     size_t workspace_bytes;
     void* stream;

@@ -13,6 +13,14 @@
 //   backward  K3 stats   g = dy act'(v);  per (instance, slab): sum g, sum g xhat  (g is parked in dresidual if asked)
 //             K4 apply   dx = rstd (g - mean(g) - xhat mean(g xhat))
 // The activation mask is taken from y when a residual was added (v is not recomputable from x alone), else from xhat.
+//
+// Two stated deviations (tests/norm_ref.py derives the per-element bounds, tests/norm_checks.py holds the kernels to them):
+//   * dx is rounded twice when dresidual is wanted in a 16-bit type behind a LeakyReLU: K3 parks g ROUNDED to the type and K4 forms
+//     dx from that rounded value, so dx carries rstd ulp(g) / 2 on top of its own final rounding (up to ~4 x the half-ulp bound of the
+//     other cases).  A design trade - it saves K4 one read of y and of dy; fp32, ReLU (g = dy or 0) and no dresidual: not affected.
+//   * the statistics are fp32 sums of x and x^2 (chains of at most 256 additions per thread, then Chan's merge): their error grows
+//     with the condition number 1 + r^2 of E[x^2] - mean^2, r = |mean| / std:  |mean' - mean| rstd <= 2^-16 (1 + r),
+//     |rstd' / rstd - 1| <= 2^-15 (1 + r^2)  - 3e-4 at r = 3, 2.7e-2 at r = 30, the limit of the sum-of-squares form.
 #include <stdlib.h>
 #include <string.h>
 
