@@ -1091,6 +1091,75 @@ size_t segm_crop_stats_workspace_bytes(int32_t channels, int32_t box_depth, int3
 int segm_crop_stats(const segm_crop_args* args);
 int segm_crop_normalize(const segm_crop_args* args);
 
+/* segm_crop_normalize with a per-channel clip in front of the subtraction: CTNormalization.run
+ * (normalization/default_normalization_schemes.py:83-95) on the box,
+ *   out = (min(max(x, lower), upper) - mean) / max(std, 1e-8)      in fp32 arithmetic, the division correctly rounded.
+ * stats32 holds 32 floats here: [0..7] mean, [8..15] std, [16..23] lower, [24..31] upper (the dataset's foreground mean, std and
+ * 0.5 / 99.5 percentiles, rounded to fp32).  A NaN stays a NaN, as under np.clip.  The crop, the relabelled seg, the label counts
+ * and every limit are segm_crop_normalize's - one kernel body serves both; `masked` must be 0 (the reference normalises CT with
+ * use_mask_for_norm=False, default_preprocessor.py:239), else SEGM_E_SHAPE. */
+int segm_crop_clip_normalize(const segm_crop_args* args);
+
+/* ------------------------------------------------------------------------------------------------
+ * The intensity fingerprint of a case (additive to ABI 10; csrc/fingerprint.hip).
+ * Replaces the reference's DefaultPreprocessor.collect_foreground_intensities (preprocessors/default_preprocessor.py:413-451):
+ * the foreground mask `segmentation[0] > 0` (:431), the compaction `images[i][foreground_mask]` (:434), the draw of num_samples
+ * of its values (:439-440) and np.min / np.max / np.median / np.percentile / np.mean of them (:441-449).  The compaction is never
+ * written: foreground voxels are addressed by their rank in C order of the logical (depth, height, width) volume.
+ *
+ * data (channels, depth, height, width) fp32, element strides for channel, z and y, unit stride along x; seg (depth, height, width)
+ * contiguous, float32 / uint8 / int16 by seg_dtype (SEGM_PREP_SEG_NONE is refused: SEGM_E_DTYPE).  A voxel is foreground where
+ * seg > 0; a NaN is not.  The three entries share the workspace: segm_fg_count fills it, the other two read what it left there,
+ * on the same stream and for the same data, seg and shape.
+ * Limits (SEGM_E_SHAPE, nothing is launched): channels in [1, SEGM_PREP_MAX_CHANNELS]; fewer than 2^31 voxels per channel;
+ * stride_y >= width.  Workspace NULL, misaligned (8 bytes) or smaller than segm_fg_workspace_bytes: SEGM_E_WORKSPACE.
+ * Workspace: per segment of SEGM_FG_SEGMENT voxels an int64 offset and one double per channel, and 96 KB of histograms per
+ * channel - 0.5 MB for one channel of 400 x 512 x 512.
+ * Integer atomics only, sums in a fixed order: two calls of every entry are bit-equal.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_FG_SEGMENT 4096
+#define SEGM_FG_MAX_RANKS 8
+#define SEGM_FG_MAX_INDICES (1 << 24)
+
+typedef struct segm_fg_args {
+    int32_t channels, depth, height, width;
+    int32_t seg_dtype, n_ranks;
+    int64_t stride_c, stride_z, stride_y;
+    const float* data;
+    const void* seg;
+    int64_t n;                     /* order_stats, gather: the foreground count segm_fg_count reported (>= 1) */
+    int64_t ranks[SEGM_FG_MAX_RANKS];   /* order_stats */
+    const int64_t* idx;            /* gather: device memory */
+    int64_t n_idx, idx_stride_c;
+    int64_t* count;                /* count: 1 int64 in device memory */
+    double* sums;                  /* count: SEGM_PREP_MAX_CHANNELS doubles in device memory */
+    float* out;                    /* order_stats: channels x SEGM_FG_MAX_RANKS floats; gather: channels x n_idx floats */
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_fg_args;
+size_t segm_fg_workspace_bytes(int32_t channels, int64_t voxels);
+
+/* One pass over the seg (and over the data where the seg is > 0): per segment of SEGM_FG_SEGMENT consecutive logical voxels the
+ * number of foreground voxels (:431), then by one workgroup the exclusive int64 offsets of the segments (kept in the workspace),
+ *   count[0] = n, the number of foreground voxels                                               (len(foreground_pixels), :435)
+ *   sums[c]  = the fp64 sum of channel c's foreground values, c < channels                     (np.mean's numerator, :442)
+ * The sums are per-workgroup partials added in a fixed order by one workgroup, as in segm_crop_stats: no floating-point atomics. */
+int segm_fg_count(const segm_fg_args* args);
+
+/* out[c * SEGM_FG_MAX_RANKS + r] = the ranks[r]-th smallest foreground value of channel c (0-based; np.sort(images[c][mask])[k]),
+ * for n_ranks in [1, SEGM_FG_MAX_RANKS] ranks in [0, n), repeats allowed (SEGM_E_SHAPE otherwise) - what np.min, np.max, np.median
+ * and np.percentile (:443-447) partition the n values for.  Radix selection on the order-preserving 32-bit key of the float bits,
+ * digits of 12 + 10 + 10 bits: three histogram passes over the data for all ranks and channels together, a one-workgroup kernel
+ * after each turns every rank into a longer prefix and a residual rank; nothing is read back in between.  -0.0 and +0.0 are equal
+ * values, either may be returned.  NaN among the foreground values is outside the contract (the reference asserts there is none, :422). */
+int segm_fg_order_stats(const segm_fg_args* args);
+
+/* out[c * n_idx + j] = channel c at the foreground voxel of rank i in C order, what images[c][mask][i] gives (:434, :440), with
+ * i = idx[j] for every channel (idx_stride_c = 0) or i = idx[c * idx_stride_c + j] (idx_stride_c >= n_idx: a draw per channel).
+ * idx: n_idx in [1, SEGM_FG_MAX_INDICES] int64 in device memory, unsorted, repeats allowed, each in [0, n).  An index outside
+ * [0, n) reads nothing and gives NaN: a caller that holds the indices on the host checks them there. */
+int segm_fg_gather(const segm_fg_args* args);
+
 /* ------------------------------------------------------------------------------------------------
  * Resampling a case to the target spacing (additive to ABI 10; csrc/resample.hip).
  * Replaces the reference's resample_data_or_seg without a separate z axis (light_training/preprocessing/resampling/

@@ -1,5 +1,5 @@
 // Preparing a case on the device: non-zero mask and bounding box, crop statistics, crop + z-score + seg relabelling
-// (C ABI: segm_nonzero_mask_bbox, segm_crop_stats, segm_crop_normalize).
+// (C ABI: segm_nonzero_mask_bbox, segm_crop_stats, segm_crop_normalize, segm_crop_clip_normalize).
 //
 // Replaces what the reference's `MultiModalityPreprocessor.run_case_npy` does on the host with numpy / scipy
 // (light_training/preprocessing/preprocessors/default_preprocessor.py:154-227): `create_nonzero_mask` and `get_bbox_from_mask`
@@ -18,7 +18,8 @@
 //                               slot, one workgroup adds the slots in a fixed order: no floating-point atomics, two calls are bit-equal.
 //   * crop_normalize_kernel     (x - mean) / max(std, 1e-8) in fp32 into the dense crop, the relabelled seg as int16, and the label
 //                               counts: -1 and 0 (nearly every voxel) are counted in registers, the rest in an LDS histogram, the
-//                               workgroup's non-zero bins go out by 64-bit integer atomic add (exact, order-free).
+//                               workgroup's non-zero bins go out by 64-bit integer atomic add (exact, order-free).  With the CLIP
+//                               flag x is first bounded per channel: CTNormalization.run (default_normalization_schemes.py:83-95).
 // Vector-memory and LDS atomics only.  The CPU emulation build (SEGM_EMU) states the same atomics with the compiler's __atomic builtins.
 #include <math.h>
 #include <stdlib.h>
@@ -310,17 +311,21 @@ __global__ void __launch_bounds__(kBlock) crop_stats_final_kernel(CropDev P) {
     }
 }
 
-__global__ void __launch_bounds__(kBlock) crop_normalize_kernel(CropDev P) {
+// CLIP: stats32[16..23] / [24..31] bound x from below / above before the subtraction (segm_crop_clip_normalize); the comparisons
+// leave a NaN a NaN, as np.clip does.  Without CLIP the arithmetic is what it was before the flag existed.
+template <bool CLIP> __global__ void __launch_bounds__(kBlock) crop_normalize_kernel(CropDev P) {
     __shared__ int32_t s_hist[SEGM_PREP_COUNT_BINS];
     __shared__ int32_t s_two[kWavesPerBlock][2];
     for (int b = threadIdx.x; b < SEGM_PREP_COUNT_BINS; b += kBlock) s_hist[b] = 0;
     __syncthreads();
-    float mean[kPrepMaxC], sd[kPrepMaxC];
+    float mean[kPrepMaxC], sd[kPrepMaxC], lower[kPrepMaxC], upper[kPrepMaxC];
 #pragma unroll
     for (int c = 0; c < kPrepMaxC; ++c) {
         mean[c] = c < P.C ? P.stats32[c] : 0.f;
         const float s = c < P.C ? P.stats32[8 + c] : 1.f;
         sd[c] = s > 1e-8f ? s : 1e-8f;
+        lower[c] = (CLIP && c < P.C) ? P.stats32[16 + c] : 0.f;
+        upper[c] = (CLIP && c < P.C) ? P.stats32[24 + c] : 0.f;
     }
     int32_t n_minus = 0, n_zero = 0;
     for (int t = 0; t < kPrepItems; ++t) {
@@ -350,8 +355,17 @@ __global__ void __launch_bounds__(kBlock) crop_normalize_kernel(CropDev P) {
                 load_data4(P, it, c, v);
                 float* o = P.out + (((int64_t)c * P.d + it.zz) * P.h + it.yy) * P.w + (it.xa - P.x0);
 #pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    if (it.in[j]) o[j] = (P.masked && lab[j] < 0) ? v[j] : (v[j] - mean[c]) / sd[c];
+                for (int j = 0; j < 4; ++j) {
+                    if (!it.in[j]) continue;
+                    if (CLIP) {
+                        float x = v[j];
+                        x = x < lower[c] ? lower[c] : x;
+                        x = x > upper[c] ? upper[c] : x;
+                        o[j] = (x - mean[c]) / sd[c];
+                    } else {
+                        o[j] = (P.masked && lab[j] < 0) ? v[j] : (v[j] - mean[c]) / sd[c];
+                    }
+                }
             }
         }
     }
@@ -465,10 +479,11 @@ extern "C" int segm_crop_stats(const segm_crop_args* a) {
     return (int)hipGetLastError();
 }
 
-extern "C" int segm_crop_normalize(const segm_crop_args* a) {
+static int crop_normalize_launch(const segm_crop_args* a, bool clip) {
     CropDev P;
     const int rc = crop_setup(a, P);
     if (rc != SEGM_OK) return rc;
+    if (clip && a->masked) return SEGM_E_SHAPE;
     if (!a->stats32 || !a->out) return SEGM_E_NULL;
     if ((uintptr_t)a->stats32 % sizeof(float) || (uintptr_t)a->out % sizeof(float)) return SEGM_E_SHAPE;
     P.labels = (a->seg_out || a->counts || a->masked) ? 1 : 0;
@@ -477,6 +492,11 @@ extern "C" int segm_crop_normalize(const segm_crop_args* a) {
     P.stats32 = a->stats32; P.out = a->out; P.seg_out = a->seg_out; P.counts = (long long*)a->counts;
     hipStream_t st = (hipStream_t)a->stream;
     if (a->counts && hipMemsetAsync(a->counts, 0, SEGM_PREP_COUNT_BINS * sizeof(int64_t), st) != hipSuccess) return (int)hipGetLastError();
-    hipLaunchKernelGGL(crop_normalize_kernel, dim3((unsigned)P.nblocks), dim3(kBlock), 0, st, P);
+    if (clip) hipLaunchKernelGGL(crop_normalize_kernel<true>, dim3((unsigned)P.nblocks), dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL(crop_normalize_kernel<false>, dim3((unsigned)P.nblocks), dim3(kBlock), 0, st, P);
     return (int)hipGetLastError();
 }
+
+extern "C" int segm_crop_normalize(const segm_crop_args* a) { return crop_normalize_launch(a, false); }
+
+extern "C" int segm_crop_clip_normalize(const segm_crop_args* a) { return crop_normalize_launch(a, true); }

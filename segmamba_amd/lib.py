@@ -301,6 +301,7 @@ EXPORTS = (
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
+    "segm_crop_clip_normalize", "segm_fg_workspace_bytes", "segm_fg_count", "segm_fg_order_stats", "segm_fg_gather",
     "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
     "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
     "segm_gauss_blur",
@@ -418,6 +419,20 @@ class CropArgs(C.Structure):
                 ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
                 ("data", C.c_void_p), ("mask", C.c_void_p), ("seg", C.c_void_p),
                 ("stats64", C.c_void_p), ("stats32", C.c_void_p), ("out", C.c_void_p), ("seg_out", C.c_void_p), ("counts", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+FG_SEGMENT, FG_MAX_RANKS, FG_MAX_INDICES = 4096, 8, 1 << 24                     # SEGM_FG_SEGMENT / _MAX_RANKS / _MAX_INDICES
+
+
+class FgArgs(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("seg_dtype", C.c_int32), ("n_ranks", C.c_int32),
+                ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("data", C.c_void_p), ("seg", C.c_void_p),
+                ("n", C.c_int64), ("ranks", C.c_int64 * FG_MAX_RANKS),
+                ("idx", C.c_void_p), ("n_idx", C.c_int64), ("idx_stride_c", C.c_int64),
+                ("count", C.c_void_p), ("sums", C.c_void_p), ("out", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
@@ -582,6 +597,11 @@ class SegmLib:
         sig("segm_crop_stats", [C.POINTER(CropArgs)], C.c_int)
         sig("segm_crop_stats_workspace_bytes", [C.c_int32] * 4, C.c_size_t)
         sig("segm_crop_normalize", [C.POINTER(CropArgs)], C.c_int)
+        sig("segm_crop_clip_normalize", [C.POINTER(CropArgs)], C.c_int)
+        sig("segm_fg_workspace_bytes", [C.c_int32, C.c_int64], C.c_size_t)
+        sig("segm_fg_count", [C.POINTER(FgArgs)], C.c_int)
+        sig("segm_fg_order_stats", [C.POINTER(FgArgs)], C.c_int)
+        sig("segm_fg_gather", [C.POINTER(FgArgs)], C.c_int)
         sig("segm_zoom", [C.POINTER(ZoomArgs)], C.c_int)
         sig("segm_zoom_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_zoom_labels", [C.POINTER(ZoomLabelsArgs)], C.c_int)

@@ -18,6 +18,8 @@ from typing import Optional
 
 import os
 
+import numpy as np
+
 import torch
 
 from . import lib as L
@@ -1805,6 +1807,122 @@ def crop_normalize(lib: L.SegmLib, data: torch.Tensor, stats32: torch.Tensor, bo
     a.stats32, a.out = stats32.data_ptr(), out.data_ptr()
     lib.check(lib.dll.segm_crop_normalize(a), "crop_normalize")
     return out, seg_out, counts
+
+
+def crop_clip_normalize(lib: L.SegmLib, data: torch.Tensor, stats32: torch.Tensor, box_start=None, box_shape=None, mask: torch.Tensor = None,
+                        seg: torch.Tensor = None, nonzero_label: int = -1, want_seg: bool = True):
+    """`crop_normalize` with the CT clip in front: (min(max(x, lower), upper) - mean) / max(std, 1e-8) in fp32.  `stats32` float32
+    (32,): mean [0:8], std [8:16], lower [16:24], upper [24:32].  There is no masked form.  -> (out, seg_out or None, counts or None)."""
+    if want_seg and mask is None:
+        raise RuntimeError("crop_clip_normalize: the relabelled seg needs the mask")
+    a, box_shape = _crop_args(data, mask, seg, box_start, box_shape, False, nonzero_label, "crop_clip_normalize")
+    _same_volume(stats32, "crop_clip_normalize: stats32", torch.float32, (32,), data.device)
+    out = torch.empty((a.channels,) + box_shape, dtype=torch.float32, device=data.device)
+    seg_out = counts = None
+    if want_seg:
+        seg_out = torch.empty(box_shape, dtype=torch.int16, device=data.device)
+        counts = torch.empty(L.PREP_COUNT_BINS, dtype=torch.int64, device=data.device)
+        a.seg_out, a.counts = seg_out.data_ptr(), counts.data_ptr()
+    a.stats32, a.out = stats32.data_ptr(), out.data_ptr()
+    lib.check(lib.dll.segm_crop_clip_normalize(a), "crop_clip_normalize")
+    return out, seg_out, counts
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the intensity fingerprint of a case (csrc/fingerprint.hip): foreground count and sums, order statistics, gather by rank
+# ---------------------------------------------------------------------------------------------------------
+class FgState:
+    """What `fg_count` leaves for `fg_order_stats` and `fg_gather`: the tensors (kept alive), the argument skeleton, the workspace"""
+
+    def __init__(self, data, seg, workspace, args):
+        self.data, self.seg, self.workspace, self.args = data, seg, workspace, args
+
+    def fresh(self) -> "L.FgArgs":
+        a = L.FgArgs()
+        C.memmove(C.byref(a), C.byref(self.args), C.sizeof(L.FgArgs))
+        return a
+
+
+def fg_count(lib: L.SegmLib, data: torch.Tensor, seg: torch.Tensor, workspace: torch.Tensor = None):
+    """data (C, D, H, W) fp32 with a unit stride along x, C <= 8; seg (D, H, W) float32 / uint8 / int16, contiguous.  Foreground is
+    seg > 0.  -> (count int64 (1,): the number n of foreground voxels; sums float64 (8,): per channel the fp64 sum of the foreground
+    values, fixed order; state for `fg_order_stats` / `fg_gather`), all on the device.  `workspace`: a uint8 tensor to use instead
+    of a fresh one (`segm_fg_workspace_bytes`)."""
+    C_, D, H, W, sc, sz, sy = _prep_data(data, "fg_count")
+    if not isinstance(seg, torch.Tensor) or seg.dtype not in _SEG_DTYPES:
+        raise RuntimeError(f"fg_count: seg must be a float32, uint8 or int16 tensor, got {getattr(seg, 'dtype', type(seg))}")
+    _same_volume(seg, "fg_count: seg", seg.dtype, (D, H, W), data.device)
+    nbytes = lib.dll.segm_fg_workspace_bytes(C_, D * H * W)
+    if nbytes == 0:
+        raise RuntimeError(f"fg_count: no workspace size for {tuple(data.shape)}")
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=data.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != data.device or not workspace.is_contiguous():
+        raise RuntimeError("fg_count: the workspace must be a contiguous tensor on the data's device")
+    count = torch.empty(1, dtype=torch.int64, device=data.device)
+    sums = torch.zeros(L.PREP_MAX_CHANNELS, dtype=torch.float64, device=data.device)
+    a = L.FgArgs()
+    a.channels, a.depth, a.height, a.width = C_, D, H, W
+    a.seg_dtype = _SEG_DTYPES[seg.dtype]
+    a.stride_c, a.stride_z, a.stride_y = sc, sz, sy
+    a.data, a.seg, a.stream = data.data_ptr(), seg.data_ptr(), L.stream_handle(data)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    state = FgState(data, seg, workspace, a)
+    b = state.fresh()
+    b.count, b.sums = count.data_ptr(), sums.data_ptr()
+    lib.check(lib.dll.segm_fg_count(b), "fg_count")
+    return count, sums, state
+
+
+def fg_order_stats(lib: L.SegmLib, state: FgState, n: int, ranks) -> torch.Tensor:
+    """-> float32 (C, len(ranks)) on the device: per channel the ranks[r]-th smallest foreground value (0-based; np.sort(fg)[k]).
+    Up to 8 ranks in [0, n), repeats allowed; `n` as `fg_count` reported it.  Exact: radix selection, three passes, no readback."""
+    ranks = [int(k) for k in ranks]
+    n = int(n)
+    if not 1 <= len(ranks) <= L.FG_MAX_RANKS:
+        raise RuntimeError(f"fg_order_stats: 1 .. {L.FG_MAX_RANKS} ranks per call, got {len(ranks)}")
+    if n < 1 or any(not 0 <= k < n for k in ranks):
+        raise RuntimeError(f"fg_order_stats: every rank must lie in [0, {n}), got {ranks}")
+    out = torch.empty(state.args.channels, L.FG_MAX_RANKS, dtype=torch.float32, device=state.data.device)
+    a = state.fresh()
+    a.n, a.n_ranks, a.out = n, len(ranks), out.data_ptr()
+    for r, k in enumerate(ranks):
+        a.ranks[r] = k
+    lib.check(lib.dll.segm_fg_order_stats(a), "fg_order_stats")
+    return out[:, :len(ranks)]
+
+
+def fg_gather(lib: L.SegmLib, state: FgState, n: int, idx) -> torch.Tensor:
+    """-> float32 (C, m) on the device: channel c at the idx[j]-th foreground voxel in C order - `images[c][mask][idx]` without the
+    compaction.  idx: int64, (m,) for all channels or (C, m) with a row per channel; unsorted, repeats allowed, each in [0, n).  A
+    numpy array or host tensor is checked against n here and uploaded; a device tensor is the caller's word (an index outside [0, n)
+    gives NaN)."""
+    n = int(n)
+    dev = state.data.device
+    if isinstance(idx, np.ndarray):
+        idx = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int64))
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() not in (1, 2):
+        raise RuntimeError(f"fg_gather: idx must be int64 of shape (m,) or (C, m), got {getattr(idx, 'dtype', type(idx))}")
+    C_ = state.args.channels
+    if idx.dim() == 2 and idx.shape[0] != C_:
+        raise RuntimeError(f"fg_gather: a per-channel idx needs {C_} rows, got {tuple(idx.shape)}")
+    m = int(idx.shape[-1])
+    if not 1 <= m <= L.FG_MAX_INDICES:
+        raise RuntimeError(f"fg_gather: 1 .. {L.FG_MAX_INDICES} indices per call, got {m}")
+    if n < 1:
+        raise RuntimeError("fg_gather: there is no foreground voxel to index")
+    if idx.device.type == "cpu":
+        if int(idx.min()) < 0 or int(idx.max()) >= n:
+            raise RuntimeError(f"fg_gather: every index must lie in [0, {n}), got [{int(idx.min())}, {int(idx.max())}]")
+        idx = idx.to(dev)
+    elif idx.device != dev:
+        raise RuntimeError(f"fg_gather: idx lies on {idx.device}, the data on {dev}")
+    idx = idx.contiguous()
+    out = torch.empty(C_, m, dtype=torch.float32, device=dev)
+    a = state.fresh()
+    a.n, a.idx, a.n_idx, a.idx_stride_c, a.out = n, idx.data_ptr(), m, (m if idx.dim() == 2 else 0), out.data_ptr()
+    lib.check(lib.dll.segm_fg_gather(a), "fg_gather")
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------
