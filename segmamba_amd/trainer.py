@@ -88,11 +88,15 @@ class TrainingState:
 
 def build_training_state(device, distributed: bool = False, local_rank: int = 0, max_steps: int = 250 * 1000,
                          model: nn.Module | None = None, amp: str | None = None, ddp: str | None = None,
-                         flat: bool | None = None, ddp_segments: int | None = None) -> TrainingState:
+                         flat: bool | None = None, ddp_segments: int | None = None,
+                         loss_fn: nn.Module | None = None) -> TrainingState:
     """ddp: "flat" | "torch" (see the module docstring; default SEGM_DDP, else "flat" where the parameter bank exists).
     flat: keep gradients / momenta in flat arrays also on one GPU (default: yes with the bank and the fused optimizer).
     ddp_segments: ddp="flat" exchanges the flat gradient array in this many segments, each started as soon as the backward pass
-    has produced it (SegmentedExchange; default SEGM_DDP_SEGMENTS, else 4); 1 = one all-reduce behind the backward pass."""
+    has produced it (SegmentedExchange; default SEGM_DDP_SEGMENTS, else 4); 1 = one all-reduce behind the backward pass.
+    loss_fn: a module called as loss_fn(logits, labels) with (B, D, H, W) int64 labels, e.g. losses.DC_and_CE_loss, in place of the
+    default cross entropy (None: the reference's nn.CrossEntropyLoss / its fused form, as before)."""
+    custom_loss = loss_fn
     amp = (amp or os.environ.get("SEGM_AMP", "bf16")).lower()
     if amp not in ("bf16", "fp16"):
         raise ValueError(f"amp must be 'bf16' or 'fp16', got {amp!r}")
@@ -143,6 +147,8 @@ def build_training_state(device, distributed: bool = False, local_rank: int = 0,
         opt = torch.optim.SGD(model.parameters(), lr=1e-2, weight_decay=3e-5, momentum=0.99, nesterov=True)
         loss_fn = nn.CrossEntropyLoss()
     sched = torch.optim.lr_scheduler.LambdaLR(opt, lambda s: (1 - min(s, max_steps - 1) / max_steps) ** 0.9)
+    if custom_loss is not None:
+        loss_fn = custom_loss
     st = TrainingState(model=model, optimizer=opt, scheduler=sched, loss_fn=loss_fn, bank=bank, world=world)
     if flat and not isinstance(model, torch.nn.parallel.DistributedDataParallel):
         bank.attach_flat_grads()
