@@ -1161,6 +1161,62 @@ int segm_fg_order_stats(const segm_fg_args* args);
 int segm_fg_gather(const segm_fg_args* args);
 
 /* ------------------------------------------------------------------------------------------------
+ * The top-k ("hard example") cross entropy (additive to ABI 10; csrc/topk_ce.hip).
+ * Replaces the reference's TopKLoss (light_training/loss/robust_ce_loss.py:19-32) and its backward:
+ *   `nn.CrossEntropyLoss(reduce=False)(inp, target)` (:29)                   -> segm_cross_entropy_map
+ *   `torch.topk(res.view((-1, )), int(num_voxels * k / 100), sorted=False)` (:31), `res.mean()` (:32)
+ *                                                                             -> segm_topk_select, the mean is arithmetic on its result
+ *   the backward of the three                                                 -> segm_cross_entropy_map_bwd
+ *
+ * logits, dlogits: (batch, classes, spatial) contiguous, one dtype (fp32 / fp16 / bf16; arithmetic in fp32), classes <= 16; labels
+ * (batch, spatial) int64; batch * spatial < 2^31 (SEGM_E_SHAPE otherwise).  NULL where a pointer is required: SEGM_E_NULL.
+ * Integer atomics only, sums in a fixed order: two calls of every entry are bit-equal.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_TOPK_RESULT_BYTES 32
+
+typedef struct segm_cross_entropy_map_args {
+    int32_t batch, classes, dtype, reserved;
+    int64_t spatial, ignore_index;
+    const void* logits;
+    const int64_t* labels;
+    float* loss_map;               /* map: out, (batch, spatial) fp32.  bwd: in, with `select` (both or neither) */
+    void* dlogits;                 /* bwd: out */
+    const float* coef;             /* bwd, optional: (batch, spatial) fp32, the upstream gradient of the map */
+    const float* scale;            /* bwd, optional: one fp32 in device memory, the upstream gradient of a reduced loss */
+    const void* select;            /* bwd, optional: the SEGM_TOPK_RESULT_BYTES segm_topk_select wrote for loss_map and kk */
+    int64_t kk;                    /* bwd with select: in [1, batch * spatial] */
+    void* stream;
+} segm_cross_entropy_map_args;
+
+/* loss_map[b, s] = logsumexp_c(x[b, :, s]) - x[b, label, s]; 0 where label == ignore_index; NaN where the label is outside
+ * [0, classes) and not ignored (segm_cross_entropy's rule: wrong labels stay loud).  One thread per voxel. */
+int segm_cross_entropy_map(const segm_cross_entropy_map_args* args);
+
+/* dlogits[b, c, s] = g (softmax_c(x)[c] - [c == label]); 0 where the label is ignored; NaN where it is wrong.  g is the product of
+ * whichever are given: coef[b, s]; scale[0]; the top-k weight of loss_map[b, s] - 1 / kk where its key is above the threshold's,
+ * (kk - n_gt) / (n_eq kk) where it is equal (the tied voxels share what is left of the kk), 0 below.  The softmax is recomputed. */
+int segm_cross_entropy_map_bwd(const segm_cross_entropy_map_args* args);
+
+/* result (SEGM_TOPK_RESULT_BYTES of device memory, 8-byte aligned, overwritten):
+ *   { float threshold; int32 pad; int64 n_gt; int64 n_eq; double sum_gt }
+ * threshold = the kk-th largest of the n values under the order of the 32-bit key of csrc/radix_hist.h (the float order; -0.0 below
+ * +0.0; a positive NaN above +inf); n_gt, n_eq = the number of keys greater than / equal to the threshold's; sum_gt = the fp64 sum of
+ * the values counted in n_gt (per-workgroup partials added by one workgroup in a fixed order).  The mean of the kk largest is
+ * (sum_gt + (kk - n_gt) threshold) / kk.  Radix selection, digits of 12 + 10 + 10 bits: a histogram pass over the values and a
+ * one-workgroup kernel per digit, a last pass for the counts and the sum; nothing is read back.
+ * values: n fp32, 1 <= n < 2^31; kk in [1, n] (SEGM_E_SHAPE otherwise).  Workspace NULL, misaligned (8 bytes) or smaller than
+ * segm_topk_select_workspace_bytes(n) (0 for an n out of range): SEGM_E_WORKSPACE. */
+typedef struct segm_topk_select_args {
+    const float* values;
+    int64_t n, kk;
+    void* result;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_topk_select_args;
+size_t segm_topk_select_workspace_bytes(int64_t n);
+int segm_topk_select(const segm_topk_select_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * Resampling a case to the target spacing (additive to ABI 10; csrc/resample.hip).
  * Replaces the reference's resample_data_or_seg without a separate z axis (light_training/preprocessing/resampling/
  * default_resampling.py:126-217 as default_preprocessor.py:187-201 calls it): skimage's resize(order 3 or 1, mode='edge',

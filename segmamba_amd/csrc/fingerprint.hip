@@ -33,21 +33,14 @@
 // histograms of 1024 bins already take 32 KB of LDS.  The workgroup's non-zero bins go to global memory by integer atomic add, so
 // the flush is as sparse as the data are narrow.  Counts are integers: exact in any order, two calls are bit-equal.
 // Vector-memory and LDS atomics only.  The CPU emulation build (SEGM_EMU) states the same atomics with the compiler's __atomic builtins.
+// The key, the atomics and the aggregation live in csrc/radix_hist.h, which csrc/topk_ce.hip shares.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "segm_device.h"
+#include "radix_hist.h"      // the key, the integer atomics, the aggregation of equal bins: shared with csrc/topk_ce.hip
 
 namespace segm {
-
-#ifdef SEGM_EMU
-static inline void fg_add_lds(uint32_t* p, uint32_t v) { __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-static inline void fg_add_glb(uint32_t* p, uint32_t v) { __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-#else
-__device__ __forceinline__ void fg_add_lds(uint32_t* p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
-__device__ __forceinline__ void fg_add_glb(uint32_t* p, uint32_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-#endif
 
 constexpr int kFgSeg = SEGM_FG_SEGMENT;
 constexpr int kFgMaxC = SEGM_PREP_MAX_CHANNELS;
@@ -84,13 +77,6 @@ struct FgDev {
     uint32_t ranks[kFgMaxR];
 };
 
-// the order-preserving key of a float and back (csrc/resample.hip: zoom_key / zoom_unkey)
-__device__ __forceinline__ uint32_t fg_key(float f) {
-    const uint32_t b = __float_as_uint(f);
-    return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
-}
-__device__ __forceinline__ float fg_unkey(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
-
 // element offset of logical voxel v inside a channel
 __device__ __forceinline__ int64_t fg_data_off(const FgDev& P, uint32_t v) {
     if (P.dense) return (int64_t)v;
@@ -126,11 +112,6 @@ __device__ __forceinline__ void fg_is4(const FgDev& P, uint32_t v, bool fg[4]) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) fg[k] = v + k < P.nvox && fg_is(P, v + k);
     }
-}
-
-template <typename T> __device__ __forceinline__ T fg_wave_sum(T v) {
-    for (int off = kWave / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // ---- count and sums per segment -----------------------------------------------------------------------------------------------------
@@ -266,26 +247,7 @@ __global__ void __launch_bounds__(kBlock) fg_hist_kernel(FgDev P) {
                 }
             }
         }
-        // the thread: the voxels in the bin of its first counted voxel become one (bin, count); the others go out on their own
-        int32_t b0 = -1;
-        uint32_t n0 = 0;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (bin[k] < 0) continue;
-            if (b0 < 0) b0 = bin[k];
-            if (bin[k] == b0) ++n0;
-            else fg_add_lds(&s_hist[bin[k]], 1u);
-        }
-        // the wave: every lane that holds the bin of the first active lane adds through that lane
-        const unsigned long long active = __ballot(b0 >= 0);
-        if (active) {                                 // uniform over the wave
-            const int leader = __builtin_ctzll(active);
-            const int32_t lb = __shfl(b0, leader);
-            const bool same = b0 == lb;
-            const uint32_t tot = fg_wave_sum(same ? n0 : 0u);
-            if (lane == leader) fg_add_lds(&s_hist[lb], tot);
-            else if (b0 >= 0 && !same) fg_add_lds(&s_hist[b0], n0);
-        }
+        fg_hist_add4(s_hist, bin, lane);
     }
     __syncthreads();
     uint32_t* g = P.hist + ((size_t)P.pass * P.C + c) * kFgHistBins;

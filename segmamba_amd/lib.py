@@ -302,6 +302,7 @@ EXPORTS = (
     "segm_ccl_select_workspace_bytes",
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
     "segm_crop_clip_normalize", "segm_fg_workspace_bytes", "segm_fg_count", "segm_fg_order_stats", "segm_fg_gather",
+    "segm_cross_entropy_map", "segm_cross_entropy_map_bwd", "segm_topk_select", "segm_topk_select_workspace_bytes",
     "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
     "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
     "segm_gauss_blur",
@@ -433,6 +434,21 @@ class FgArgs(C.Structure):
                 ("n", C.c_int64), ("ranks", C.c_int64 * FG_MAX_RANKS),
                 ("idx", C.c_void_p), ("n_idx", C.c_int64), ("idx_stride_c", C.c_int64),
                 ("count", C.c_void_p), ("sums", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+TOPK_RESULT_BYTES = 32                                                         # SEGM_TOPK_RESULT_BYTES
+
+
+class CrossEntropyMapArgs(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("classes", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32),
+                ("spatial", C.c_int64), ("ignore_index", C.c_int64),
+                ("logits", C.c_void_p), ("labels", C.c_void_p), ("loss_map", C.c_void_p), ("dlogits", C.c_void_p),
+                ("coef", C.c_void_p), ("scale", C.c_void_p), ("select", C.c_void_p), ("kk", C.c_int64), ("stream", C.c_void_p)]
+
+
+class TopkSelectArgs(C.Structure):
+    _fields_ = [("values", C.c_void_p), ("n", C.c_int64), ("kk", C.c_int64), ("result", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
@@ -602,6 +618,10 @@ class SegmLib:
         sig("segm_fg_count", [C.POINTER(FgArgs)], C.c_int)
         sig("segm_fg_order_stats", [C.POINTER(FgArgs)], C.c_int)
         sig("segm_fg_gather", [C.POINTER(FgArgs)], C.c_int)
+        sig("segm_cross_entropy_map", [C.POINTER(CrossEntropyMapArgs)], C.c_int)
+        sig("segm_cross_entropy_map_bwd", [C.POINTER(CrossEntropyMapArgs)], C.c_int)
+        sig("segm_topk_select", [C.POINTER(TopkSelectArgs)], C.c_int)
+        sig("segm_topk_select_workspace_bytes", [C.c_int64], C.c_size_t)
         sig("segm_zoom", [C.POINTER(ZoomArgs)], C.c_int)
         sig("segm_zoom_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_zoom_labels", [C.POINTER(ZoomLabelsArgs)], C.c_int)

@@ -1,20 +1,24 @@
-"""The reference's nnU-Net training loss (light_training/loss/): Dice + cross entropy under the reference's names - host side.
+"""The reference's nnU-Net training loss (light_training/loss/): Dice, cross entropy and top-k cross entropy under the reference's names.
 
-  * `SoftDiceLoss`, `MemoryEfficientSoftDiceLoss` (dice.py:9-116), `RobustCrossEntropyLoss` (robust_ce_loss.py:6-16), `DC_and_CE_loss`
-    (compound_losses.py:8-57), `DeepSupervisionWrapper` (deepsupervision.py:5-36) and `softmax_helper_dim1` (helpers.py), with the
-    reference's constructor signatures;
-  * both Dice classes and the CE term are built on five sums, `dice_ce_sums`: per (b, c) I = sum m p_c [y = c], P = sum m p_c,
-    G = sum m [y = c] and, per b, the cross-entropy sum and the number of valid voxels.  SoftDiceLoss' tp, fp, fn are I, P - I, G - I;
-    what follows the sums (batch_dice, do_bg, smooth, clip_tp, the clip of the denominator, the mean, the weights) is arithmetic on
-    (B, C) tensors;
+  * `SoftDiceLoss`, `MemoryEfficientSoftDiceLoss` (dice.py:9-116), `RobustCrossEntropyLoss`, `TopKLoss` (robust_ce_loss.py:6-32),
+    `DC_and_CE_loss`, `DC_and_topk_loss` (compound_losses.py:8-57, 103-151), `DeepSupervisionWrapper` (deepsupervision.py:5-36) and
+    `softmax_helper_dim1` (helpers.py), with the reference's constructor signatures;
+  * both Dice classes and the CE term of `DC_and_CE_loss` are built on five sums, `dice_ce_sums`: per (b, c) I = sum m p_c [y = c],
+    P = sum m p_c, G = sum m [y = c] and, per b, the cross-entropy sum and the number of valid voxels.  SoftDiceLoss' tp, fp, fn are
+    I, P - I, G - I; what follows the sums (batch_dice, do_bg, smooth, clip_tp, the clip of the denominator, the mean, the weights) is
+    arithmetic on (B, C) tensors;
   * the sums are computed in ATen for CPU tensors only.  The library has no kernel for them, and no ATen fall-back on the device:
-    everything that needs the sums refuses device tensors with NotImplementedError.  `RobustCrossEntropyLoss` runs on the device, on
-    `train_ops.cross_entropy`.
+    everything that needs the sums refuses device tensors with NotImplementedError;
+  * on the device run `RobustCrossEntropyLoss` (on `train_ops.cross_entropy`), `TopKLoss` (on `train_ops.topk_cross_entropy`: the
+    per-voxel map, an exact radix selection, a per-voxel backward - csrc/topk_ce.hip) and `DC_and_topk_loss` with `weight_dice=0`,
+    which never asks for the sums.
 
 Stated deviations from the reference: sum_gt is an integer count for both Dice classes; a batch whose voxels are all ignored gives 0
-for the CE term (the reference's `num_fg > 0` rule); a voxel the CE term ignores is left out of the Dice term too; a label outside
-[0, classes) that is not ignored gives NaN instead of an indexing error.
-Not here: DC_and_BCE_loss, DC_and_topk_loss, TopKLoss, AutoDeepSupervision, one-hot targets, double backward.
+for the CE term (the reference's `num_fg > 0` rule; the top-k term needs no rule: its map is all zeros); a voxel the CE term of
+`DC_and_CE_loss` ignores is left out of the Dice term too; a label outside [0, classes) that is not ignored gives NaN instead of an
+indexing error; `TopKLoss` raises ValueError where k selects no voxel (the reference returns the NaN of an empty mean), and among
+voxels tied with the k-th largest loss each gets an equal share of the gradient where `torch.topk` picks some of them (same value).
+Not here: DC_and_BCE_loss, AutoDeepSupervision, class weights, label smoothing, one-hot targets, double backward.
 """
 from __future__ import annotations
 
@@ -219,6 +223,23 @@ class RobustCrossEntropyLoss(nn.Module):
         return train_ops.cross_entropy(input, target.long(), self.ignore_index)
 
 
+class TopKLoss(nn.Module):
+    """reference robust_ce_loss.py:19-32 on train_ops.topk_cross_entropy: the mean of the largest k % of the per-voxel cross entropies,
+    the ignored voxels counted with loss 0.  Takes the float (B, 1, ...) target, or (B, ...)."""
+
+    def __init__(self, weight=None, ignore_index: int = -100, k: float = 10, label_smoothing: float = 0):
+        super().__init__()
+        _check_ce_kwargs(weight, None, None, "mean", label_smoothing, "TopKLoss")
+        self.ignore_index, self.k = ignore_index, k
+
+    def forward(self, inp: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        if target.dim() == inp.dim():
+            if target.shape[1] != 1:
+                raise ValueError(f"TopKLoss: target must be (B, 1, *spatial) or (B, *spatial), got {tuple(target.shape)}")
+            target = target[:, 0]
+        return train_ops.topk_cross_entropy(inp, target.long(), self.k, self.ignore_index)
+
+
 class DC_and_CE_loss(nn.Module):
     """reference compound_losses.py:8-57.  Both terms come from the same five sums; `ignore_label` goes into them instead of a mask and
     a cloned target, and the CE term is ce_sum / max(count, 1): 0 when every voxel is ignored."""
@@ -247,6 +268,35 @@ class DC_and_CE_loss(nn.Module):
         if self.weight_dice != 0:
             result = result + self.weight_dice * self.dc.from_sums(intersect, sum_pred, sum_gt)
         return result
+
+
+class DC_and_topk_loss(nn.Module):
+    """reference compound_losses.py:103-151.  The Dice term is `SoftDiceLoss` on the sums (CPU tensors; it refuses device tensors),
+    with the ignored voxels masked out as the reference does; it is skipped when `weight_dice == 0`, which then runs on the device.
+    The reference's `num_fg > 0` rule needs no readback: if every voxel is ignored the map is all zeros and the top-k mean is 0."""
+
+    def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None):
+        super().__init__()
+        ce_kwargs = dict(ce_kwargs)
+        if ignore_label is not None:
+            ce_kwargs["ignore_index"] = ignore_label
+        self.weight_dice, self.weight_ce, self.ignore_label = weight_dice, weight_ce, ignore_label
+        self.ce = TopKLoss(**ce_kwargs)
+        self.dc = SoftDiceLoss(apply_nonlin=softmax_helper_dim1, **soft_dice_kwargs)
+
+    def forward(self, net_output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        mask = None
+        if self.ignore_label is not None:
+            if target.dim() != net_output.dim() or target.shape[1] != 1:
+                raise NotImplementedError("DC_and_topk_loss: ignore_label needs a label map (B, 1, ...), not a one-hot target")
+            mask = target != self.ignore_label
+        result = None
+        if self.weight_ce != 0:
+            result = self.weight_ce * self.ce(net_output, target)
+        if self.weight_dice != 0:
+            dc_loss = self.weight_dice * self.dc(net_output, target, loss_mask=mask)
+            result = dc_loss if result is None else result + dc_loss
+        return net_output.new_zeros((), dtype=torch.float32) if result is None else result
 
 
 class DeepSupervisionWrapper(nn.Module):

@@ -1057,6 +1057,93 @@ def cross_entropy(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Tensor, ig
     return tot[0], tot[1], dlogits
 
 
+def _ce_map_args(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int, what: str):
+    if not cross_entropy_supported(logits, labels):
+        raise RuntimeError(f"{what}: logits (B, C <= 16, *spatial) fp32 / fp16 / bf16 and int64 labels (B, *spatial)")
+    if labels.device != logits.device:
+        raise RuntimeError(f"{what}: the labels lie on {labels.device}, the logits on {logits.device}")
+    logits, labels = logits.contiguous(), labels.contiguous()
+    B, Cc = logits.shape[:2]
+    S = logits.numel() // (B * Cc)
+    if B * S >= 1 << 31:
+        raise RuntimeError(f"{what}: {B * S} voxels, fewer than 2^31 are supported")
+    a = L.CrossEntropyMapArgs()
+    a.batch, a.classes, a.dtype = B, Cc, L.dtype_code(logits)
+    a.spatial, a.ignore_index = S, ignore_index
+    a.logits, a.labels = logits.data_ptr(), labels.data_ptr()
+    a.stream = L.stream_handle(logits)
+    return a, logits, labels
+
+
+def cross_entropy_map(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
+    """-> the per-voxel cross entropy, fp32 (B, *spatial): logsumexp - x[label]; 0 where the label is ignored; NaN where it is outside
+    [0, C) and not ignored.  `F.cross_entropy(reduction="none")` without the fp32 copy of the logits."""
+    a, logits, labels = _ce_map_args(logits, labels, ignore_index, "cross_entropy_map")
+    out = torch.empty(labels.shape, dtype=torch.float32, device=logits.device)
+    a.loss_map = out.data_ptr()
+    lib.check(lib.dll.segm_cross_entropy_map(a), "cross_entropy_map")
+    return out
+
+
+def topk_select(lib: L.SegmLib, values: torch.Tensor, kk: int, workspace: torch.Tensor = None) -> torch.Tensor:
+    """values: contiguous fp32, n < 2^31 elements; kk in [1, n].  -> 32 bytes on the device as int64 (4,): view(float32)[0] the kk-th
+    largest value (a positive NaN sorts above +inf), [1] n_gt and [2] n_eq, the number of values above / equal to it, view(float64)[3]
+    the fp64 sum of the values above.  Exact: radix selection, three histogram passes and one for the sum, nothing is read back."""
+    if not isinstance(values, torch.Tensor) or values.dtype != torch.float32 or not values.is_contiguous():
+        raise RuntimeError("topk_select: values must be a contiguous fp32 tensor")
+    n, kk = values.numel(), int(kk)
+    if not 1 <= n < 1 << 31:
+        raise RuntimeError(f"topk_select: 1 .. 2^31 - 1 values, got {n}")
+    if not 1 <= kk <= n:
+        raise RuntimeError(f"topk_select: kk must lie in [1, {n}], got {kk}")
+    nbytes = lib.dll.segm_topk_select_workspace_bytes(n)
+    if workspace is None:
+        workspace = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=values.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != values.device or not workspace.is_contiguous():
+        raise RuntimeError("topk_select: the workspace must be a contiguous tensor on the values' device")
+    result = torch.empty(L.TOPK_RESULT_BYTES // 8, dtype=torch.int64, device=values.device)
+    a = L.TopkSelectArgs()
+    a.values, a.n, a.kk, a.result = values.data_ptr(), n, kk, result.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    a.stream = L.stream_handle(values)
+    lib.check(lib.dll.segm_topk_select(a), "topk_select")
+    return result
+
+
+def cross_entropy_map_bwd(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100,
+                          coef: torch.Tensor = None, scale: torch.Tensor = None, loss_map: torch.Tensor = None,
+                          select: torch.Tensor = None, kk: int = 0) -> torch.Tensor:
+    """-> dlogits = g (softmax - onehot) in the logits' dtype and shape; 0 where the label is ignored, NaN where it is wrong.  g is the
+    product of whichever are given: `coef` fp32 (B, *spatial); `scale`, a 1-element fp32 tensor; the top-k weight formed from
+    `loss_map` (what `cross_entropy_map` returned), `select` (what `topk_select` returned for it) and `kk`."""
+    a, logits, labels = _ce_map_args(logits, labels, ignore_index, "cross_entropy_map_bwd")
+    dev = logits.device
+    if coef is not None:
+        if coef.dtype != torch.float32 or tuple(coef.shape) != tuple(labels.shape) or coef.device != dev:
+            raise RuntimeError("cross_entropy_map_bwd: coef must be fp32 of the labels' shape on the logits' device")
+        coef = coef.contiguous()
+        a.coef = coef.data_ptr()
+    if scale is not None:
+        if scale.dtype != torch.float32 or scale.numel() != 1 or scale.device != dev:
+            raise RuntimeError("cross_entropy_map_bwd: scale must be a 1-element fp32 tensor on the logits' device")
+        a.scale = scale.data_ptr()
+    if (loss_map is None) != (select is None):
+        raise RuntimeError("cross_entropy_map_bwd: the top-k weight needs both loss_map and select")
+    if select is not None:
+        if loss_map.dtype != torch.float32 or tuple(loss_map.shape) != tuple(labels.shape) or loss_map.device != dev or \
+                not loss_map.is_contiguous():
+            raise RuntimeError("cross_entropy_map_bwd: loss_map must be contiguous fp32 of the labels' shape on the logits' device")
+        if select.dtype != torch.int64 or select.numel() != L.TOPK_RESULT_BYTES // 8 or select.device != dev or not select.is_contiguous():
+            raise RuntimeError("cross_entropy_map_bwd: select must be the int64 (4,) tensor topk_select returned")
+        if not 1 <= int(kk) <= labels.numel():
+            raise RuntimeError(f"cross_entropy_map_bwd: kk must lie in [1, {labels.numel()}], got {kk}")
+        a.loss_map, a.select, a.kk = loss_map.data_ptr(), select.data_ptr(), int(kk)
+    dlogits = torch.empty_like(logits)
+    a.dlogits = dlogits.data_ptr()
+    lib.check(lib.dll.segm_cross_entropy_map_bwd(a), "cross_entropy_map_bwd")
+    return dlogits
+
+
 # ---------------------------------------------------------------------------------------------------------
 # single-token decode steps
 # ---------------------------------------------------------------------------------------------------------

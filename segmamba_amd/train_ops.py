@@ -1,7 +1,10 @@
 """Device-side training-step glue: fused cross entropy and clip + SGD, on the HIP library.
 
   * `cross_entropy(logits, labels)` == `nn.CrossEntropyLoss()(logits, labels)` (reference 3_train.py:48,62; mean
-    reduction, ignore_index -100) as one kernel that also produces d(loss)/d(logits);
+    reduction, ignore_index -100) as one kernel that also produces d(loss)/d(logits); `reduction="none"` / `"sum"` give the per-voxel
+    map and its sum on csrc/topk_ce.hip, whose backward takes a gradient per voxel;
+  * `topk_cross_entropy(logits, labels, k)` == the reference's `TopKLoss` (light_training/loss/robust_ce_loss.py:19-32): the map, an
+    exact radix selection of the k-th largest value, and a backward that forms the top-k weight in the kernel;
   * `FusedClipSGD` == `torch.nn.utils.clip_grad_norm_(params, max_norm)` + `torch.optim.SGD(..., nesterov=True).step()`
     (reference light_training/trainer.py:461-470, 3_train.py:51-52) in two passes over the parameters.  State layout
     (`momentum_buffer` per parameter) and `param_groups` are those of torch.optim.SGD, so checkpoints interchange.
@@ -30,28 +33,102 @@ class _CrossEntropy(torch.autograd.Function):
         return dlogits * (grad / count).to(dlogits.dtype), None, None
 
 
-def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100) -> torch.Tensor:
-    """Mean cross entropy over the class axis (dim 1); fp32 scalar.  Under autocast the logits are used in the dtype they
-    arrive in (the kernel computes in fp32 either way), which skips ATen's fp32 copy of the logits."""
-    from . import lib as L
-    if not L.on_device(logits):
-        return F.cross_entropy(logits.float(), labels, ignore_index=ignore_index)
+class _CrossEntropyMap(torch.autograd.Function):
+    """the per-voxel map (reduce False) or its sum (reduce True); the backward recomputes the softmax from the logits"""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, reduce):
+        from . import lib as L, ops_raw
+        ctx.save_for_backward(logits, labels)
+        ctx.ignore_index, ctx.reduce = ignore_index, reduce
+        loss_map = ops_raw.cross_entropy_map(L.get_lib(), logits, labels, ignore_index)
+        return loss_map.sum() if reduce else loss_map
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import lib as L, ops_raw
+        logits, labels = ctx.saved_tensors
+        grad = grad.float()
+        kw = dict(scale=grad.reshape(1).contiguous()) if ctx.reduce else dict(coef=grad)
+        return ops_raw.cross_entropy_map_bwd(L.get_lib(), logits, labels, ctx.ignore_index, **kw), None, None, None
+
+
+class _TopKCrossEntropy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, ignore_index, kk):
+        from . import lib as L, ops_raw
+        hip = L.get_lib()
+        loss_map = ops_raw.cross_entropy_map(hip, logits, labels, ignore_index)
+        select = ops_raw.topk_select(hip, loss_map.view(-1), kk)
+        ctx.save_for_backward(logits, labels, loss_map, select)
+        ctx.ignore_index, ctx.kk = ignore_index, kk
+        # {threshold; n_gt; n_eq; sum_gt}: the mean of the kk largest, the values tied with the threshold filling what n_gt leaves
+        threshold, n_gt, sum_gt = select.view(torch.float32)[0], select[1], select.view(torch.float64)[3]
+        return ((sum_gt + (kk - n_gt).double() * threshold.double()) / kk).float()
+
+    @staticmethod
+    def backward(ctx, grad):
+        from . import lib as L, ops_raw
+        logits, labels, loss_map, select = ctx.saved_tensors
+        return ops_raw.cross_entropy_map_bwd(L.get_lib(), logits, labels, ctx.ignore_index, scale=grad.float().reshape(1).contiguous(),
+                                             loss_map=loss_map, select=select, kk=ctx.kk), None, None, None
+
+
+def _check_ce_inputs(logits, labels, what):
     from . import ops_raw
     if not ops_raw.cross_entropy_supported(logits, labels):
-        raise RuntimeError("cross_entropy: expected logits (B, C <= 16, *spatial) fp32 / fp16 / bf16 and int64 labels (B, *spatial)")
+        raise RuntimeError(f"{what}: expected logits (B, C <= 16, *spatial) fp32 / fp16 / bf16 and int64 labels (B, *spatial)")
+
+
+def cross_entropy(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = -100, reduction: str = "mean") -> torch.Tensor:
+    """Cross entropy over the class axis (dim 1), fp32: the mean over the counted voxels ("mean"), the (B, *spatial) map with 0 at
+    the ignored voxels ("none") or its sum ("sum").  Under autocast the logits are used in the dtype they arrive in (the kernels
+    compute in fp32 either way), which skips ATen's fp32 copy of the logits."""
+    from . import lib as L
+    if reduction not in ("mean", "none", "sum"):
+        raise ValueError(f"cross_entropy: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
+    if not L.on_device(logits):
+        return F.cross_entropy(logits.float(), labels, ignore_index=ignore_index, reduction=reduction)
+    _check_ce_inputs(logits, labels, "cross_entropy")
     with torch.autocast("cuda", enabled=False):
-        return _CrossEntropy.apply(logits, labels, ignore_index)
+        if reduction == "mean":
+            return _CrossEntropy.apply(logits, labels, ignore_index)
+        return _CrossEntropyMap.apply(logits, labels, ignore_index, reduction == "sum")
+
+
+def topk_cross_entropy(logits: torch.Tensor, labels: torch.Tensor, k: float = 10, ignore_index: int = -100) -> torch.Tensor:
+    """The mean of the largest k % of the per-voxel cross entropies (reference light_training/loss/robust_ce_loss.py:27-32); fp32
+    scalar.  kk = int(n k / 100) of the n = B * spatial voxels, the ignored ones included with loss 0, as the reference counts.
+    kk == 0 raises ValueError (the reference returns the NaN of an empty mean).  Among voxels tied with the kk-th largest loss every
+    one gets the share (kk - n_gt) / n_eq of the gradient where torch.topk picks some kk - n_gt of them: the value is the same, the
+    gradient a valid subgradient, and two calls agree.  On the device nothing is read back."""
+    from . import lib as L
+    if labels.dim() < 1 or labels.numel() == 0:
+        raise ValueError("topk_cross_entropy: empty labels")
+    kk = int(labels.numel() * k / 100)
+    if kk <= 0:
+        raise ValueError(f"topk_cross_entropy: k = {k} % of {labels.numel()} voxels selects none")
+    if kk > labels.numel():
+        raise ValueError(f"topk_cross_entropy: k = {k} % selects more than the {labels.numel()} voxels")
+    if not L.on_device(logits):
+        res = F.cross_entropy(logits.float(), labels, ignore_index=ignore_index, reduction="none")
+        return torch.topk(res.view((-1,)), kk, sorted=False)[0].mean()
+    _check_ce_inputs(logits, labels, "topk_cross_entropy")
+    with torch.autocast("cuda", enabled=False):
+        return _TopKCrossEntropy.apply(logits, labels, ignore_index, kk)
 
 
 class CrossEntropyLoss(torch.nn.Module):
     """Drop-in for the `nn.CrossEntropyLoss()` of the reference trainer (3_train.py:48)."""
 
-    def __init__(self, ignore_index: int = -100):
+    def __init__(self, ignore_index: int = -100, reduction: str = "mean"):
         super().__init__()
-        self.ignore_index = ignore_index
+        if reduction not in ("mean", "none", "sum"):
+            raise ValueError(f"CrossEntropyLoss: reduction must be 'mean', 'none' or 'sum', got {reduction!r}")
+        self.ignore_index, self.reduction = ignore_index, reduction
 
     def forward(self, logits, labels):
-        return cross_entropy(logits, labels, self.ignore_index)
+        return cross_entropy(logits, labels, self.ignore_index, self.reduction)
 
 
 class FusedClipSGD(torch.optim.Optimizer):
