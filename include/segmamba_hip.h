@@ -1217,6 +1217,65 @@ size_t segm_topk_select_workspace_bytes(int64_t n);
 int segm_topk_select(const segm_topk_select_args* args);
 
 /* ------------------------------------------------------------------------------------------------
+ * The region-based loss: sigmoid Dice + BCE sums and their gradient (additive to ABI 10; csrc/region_loss.hip).
+ * Replaces what the reference's DC_and_BCE_loss (light_training/loss/compound_losses.py:84-100) and its Dice classes
+ * (light_training/loss/dice.py:72-113) run over the volume: the sigmoid, the products with the one-hot region target and the loss
+ * mask, the reductions over the spatial axes, BCEWithLogitsLoss, and the backward of all of them.  What follows the sums is
+ * arithmetic on (batch, regions) tensors and stays with the caller.
+ *
+ * With p = sigmoid(x), the region target t(b, r, v) and the validity m(b, v), per (b, r)
+ *     I = sum_v m p t     P = sum_v m p     G = sum_v m t     E = sum_v m (max(x, 0) - x t + log1p(exp(-|x|)))
+ * and per b the count N = sum_v m.
+ *
+ * logits: (batch, regions, depth, height, width), regions in [1, SEGM_REGION_MAX_REGIONS], fp32 / fp16 / bf16 (arithmetic in
+ * fp32), element strides for batch, region, z and y, stride_x == 1 (SEGM_E_SHAPE otherwise), aligned to its element size;
+ * depth * height * width < 2^31.  A caller with fewer spatial axes passes 1 for the missing ones.
+ * target, dense, by target_kind:
+ *   SEGM_REGION_LABELS_*: a label map (batch, depth, height, width); t = (masks[r] >> label) & 1.  With has_ignore a label equal
+ *     to ignore_label (any value; compared before the range check) has m = 0.  Any other label outside [0, 32), or a float label
+ *     that is no integer, puts NaN into that sample's I, P and E (a wrong label stays loud) and into its voxel of dlogits.
+ *   SEGM_REGION_PLANES_*: (batch, regions + ignore_plane, depth, height, width), the values used as they are (soft targets
+ *     work); with ignore_plane = 1 the last plane L gives m = ((1 - L) != 0), the reference's use_ignore_label (:87).
+ * Per-workgroup partial rows in the workspace, added by one workgroup per sample in a fixed order, all in fp64; no floating-point
+ * atomic: two calls on the same tensors are bit-equal.  The aligned route (16-byte packets of logits) and the per-voxel route
+ * compute every voxel's terms alike but add them in another order: no bit-equality between differently aligned views.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_REGION_MAX_REGIONS 8
+enum segm_region_target {
+    SEGM_REGION_LABELS_I64 = 0, SEGM_REGION_LABELS_I16 = 1, SEGM_REGION_LABELS_U8 = 2, SEGM_REGION_LABELS_F32 = 3,
+    SEGM_REGION_PLANES_U8 = 4, SEGM_REGION_PLANES_F32 = 5
+};
+
+typedef struct segm_region_loss_args {
+    int32_t batch, regions, dtype, target_kind;
+    int32_t depth, height, width;
+    int32_t ignore_plane;          /* planes: 1 if the target has regions + 1 planes; labels: must be 0 */
+    int32_t has_ignore, reserved;  /* labels: whether ignore_label counts */
+    int64_t ignore_label;
+    int64_t stride_b, stride_r, stride_z, stride_y, stride_x;      /* of logits, in elements; stride_x must be 1 */
+    uint32_t masks[SEGM_REGION_MAX_REGIONS];                       /* labels: bit l of masks[r] = label l belongs to region r */
+    const void* logits;
+    const void* target;
+    double* sums;                  /* fwd: out, fp64 [I (batch, regions) | P | G | E | N (batch)], 4 batch regions + batch values */
+    const float* g_i;              /* bwd: (batch, regions) fp32, dense, in device memory: d loss / d I, / d P, / d E */
+    const float* g_p;
+    const float* g_e;
+    void* dlogits;                 /* bwd: out, (batch, regions, depth, height, width) dense, the logits' dtype */
+    void* workspace;     size_t workspace_bytes;                    /* fwd only */
+    void* stream;
+} segm_region_loss_args;
+
+/* 0 for a shape out of range.  Workspace NULL, misaligned (8 bytes) or smaller than this: SEGM_E_WORKSPACE. */
+size_t segm_region_loss_workspace_bytes(int32_t batch, int32_t regions, int64_t voxels);
+
+/* The five sums (compound_losses.py:84-100 and dice.py:72-113 up to the sums).  Two launches, nothing is read back. */
+int segm_region_loss_fwd(const segm_region_loss_args* args);
+
+/* dlogits = m (p (1 - p) (g_i t + g_p) + g_e (p - t)), exactly 0 where m = 0; the sigmoid is recomputed (the backward of
+ * compound_losses.py:84-100 and dice.py:72-113 given the gradients of the loss by the sums).  One launch, nothing is read back. */
+int segm_region_loss_bwd(const segm_region_loss_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * Resampling a case to the target spacing (additive to ABI 10; csrc/resample.hip).
  * Replaces the reference's resample_data_or_seg without a separate z axis (light_training/preprocessing/resampling/
  * default_resampling.py:126-217 as default_preprocessor.py:187-201 calls it): skimage's resize(order 3 or 1, mode='edge',

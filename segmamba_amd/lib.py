@@ -303,6 +303,7 @@ EXPORTS = (
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
     "segm_crop_clip_normalize", "segm_fg_workspace_bytes", "segm_fg_count", "segm_fg_order_stats", "segm_fg_gather",
     "segm_cross_entropy_map", "segm_cross_entropy_map_bwd", "segm_topk_select", "segm_topk_select_workspace_bytes",
+    "segm_region_loss_workspace_bytes", "segm_region_loss_fwd", "segm_region_loss_bwd",
     "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
     "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
     "segm_gauss_blur",
@@ -449,6 +450,24 @@ class CrossEntropyMapArgs(C.Structure):
 
 class TopkSelectArgs(C.Structure):
     _fields_ = [("values", C.c_void_p), ("n", C.c_int64), ("kk", C.c_int64), ("result", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+REGION_MAX_REGIONS = 8                                                         # SEGM_REGION_MAX_REGIONS
+# enum segm_region_target, by the target's dtype (bool is viewed as uint8 by the caller)
+REGION_LABELS = {torch.int64: 0, torch.int16: 1, torch.uint8: 2, torch.float32: 3}
+REGION_PLANES = {torch.uint8: 4, torch.float32: 5}
+
+
+class RegionLossArgs(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("regions", C.c_int32), ("dtype", C.c_int32), ("target_kind", C.c_int32),
+                ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("ignore_plane", C.c_int32),
+                ("has_ignore", C.c_int32), ("reserved", C.c_int32), ("ignore_label", C.c_int64),
+                ("stride_b", C.c_int64), ("stride_r", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_x", C.c_int64),
+                ("masks", C.c_uint32 * REGION_MAX_REGIONS),
+                ("logits", C.c_void_p), ("target", C.c_void_p), ("sums", C.c_void_p),
+                ("g_i", C.c_void_p), ("g_p", C.c_void_p), ("g_e", C.c_void_p), ("dlogits", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
@@ -622,6 +641,9 @@ class SegmLib:
         sig("segm_cross_entropy_map_bwd", [C.POINTER(CrossEntropyMapArgs)], C.c_int)
         sig("segm_topk_select", [C.POINTER(TopkSelectArgs)], C.c_int)
         sig("segm_topk_select_workspace_bytes", [C.c_int64], C.c_size_t)
+        sig("segm_region_loss_workspace_bytes", [C.c_int32, C.c_int32, C.c_int64], C.c_size_t)
+        sig("segm_region_loss_fwd", [C.POINTER(RegionLossArgs)], C.c_int)
+        sig("segm_region_loss_bwd", [C.POINTER(RegionLossArgs)], C.c_int)
         sig("segm_zoom", [C.POINTER(ZoomArgs)], C.c_int)
         sig("segm_zoom_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_zoom_labels", [C.POINTER(ZoomLabelsArgs)], C.c_int)

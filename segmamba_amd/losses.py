@@ -1,4 +1,5 @@
-"""The reference's nnU-Net training loss (light_training/loss/): Dice, cross entropy and top-k cross entropy under the reference's names.
+"""The reference's nnU-Net training loss (light_training/loss/): Dice, cross entropy, top-k cross entropy and the region-based
+sigmoid Dice + BCE under the reference's names.
 
   * `SoftDiceLoss`, `MemoryEfficientSoftDiceLoss` (dice.py:9-116), `RobustCrossEntropyLoss`, `TopKLoss` (robust_ce_loss.py:6-32),
     `DC_and_CE_loss`, `DC_and_topk_loss` (compound_losses.py:8-57, 103-151), `DeepSupervisionWrapper` (deepsupervision.py:5-36) and
@@ -7,22 +8,33 @@
     P = sum m p_c, G = sum m [y = c] and, per b, the cross-entropy sum and the number of valid voxels.  SoftDiceLoss' tp, fp, fn are
     I, P - I, G - I; what follows the sums (batch_dice, do_bg, smooth, clip_tp, the clip of the denominator, the mean, the weights) is
     arithmetic on (B, C) tensors;
-  * the sums are computed in ATen for CPU tensors only.  The library has no kernel for them, and no ATen fall-back on the device:
-    everything that needs the sums refuses device tensors with NotImplementedError;
+  * these softmax sums are computed in ATen for CPU tensors only.  The library has no kernel for them, and no ATen fall-back on the
+    device: everything that needs them refuses device tensors with NotImplementedError;
   * on the device run `RobustCrossEntropyLoss` (on `train_ops.cross_entropy`), `TopKLoss` (on `train_ops.topk_cross_entropy`: the
     per-voxel map, an exact radix selection, a per-voxel backward - csrc/topk_ce.hip) and `DC_and_topk_loss` with `weight_dice=0`,
-    which never asks for the sums.
+    which never asks for the sums;
+  * `DC_and_BCE_loss` (compound_losses.py:60-100), the region-based loss - one sigmoid output per region, Dice on the sigmoids plus
+    BCEWithLogitsLoss - runs on the device on `region_sums`: per (b, r) I = sum m p t, P = sum m p, G = sum m t,
+    E = sum m (max(x, 0) - x t + log1p(exp(-|x|))) and per b N = sum m, from csrc/region_loss.hip (one pass over the logits and the
+    target for all regions, fp64 sums in a fixed order, a one-launch backward that recomputes the sigmoid).  Two target modes: the
+    reference's one-hot planes (B, R, ...) - or (B, R + 1, ...) with `use_ignore_label`, the last plane being the ignore mask - and,
+    with `regions=`, a label map (B, ...) as the feeders produce it: a region is a set of labels (`BRATS_REGIONS`: TC, WT, ET of
+    3_train.py:68-72), the region target is never built.  `region_targets` is `convert_labels` for CPU callers and tests.  The Dice
+    term goes through `from_sums` of this module's Dice classes, whose own `forward` keeps refusing device tensors.
 
 Stated deviations from the reference: sum_gt is an integer count for both Dice classes; a batch whose voxels are all ignored gives 0
 for the CE term (the reference's `num_fg > 0` rule; the top-k term needs no rule: its map is all zeros); a voxel the CE term of
 `DC_and_CE_loss` ignores is left out of the Dice term too; a label outside [0, classes) that is not ignored gives NaN instead of an
 indexing error; `TopKLoss` raises ValueError where k selects no voxel (the reference returns the NaN of an empty mean), and among
 voxels tied with the k-th largest loss each gets an equal share of the gradient where `torch.topk` picks some of them (same value).
-Not here: DC_and_BCE_loss, AutoDeepSupervision, class weights, label smoothing, one-hot targets, double backward.
+`DC_and_BCE_loss`: in label mode a label outside [0, 32) that is not ignored, or a float label that is no integer, gives NaN; the
+sums are float64 and the loss is returned as float32; `weight`, `pos_weight` and reductions other than the mean are refused; while a
+graph is being captured the device path raises RuntimeError before any launch (capture of this loss is unsupported).
+Not here: AutoDeepSupervision, class weights, label smoothing, one-hot targets for the softmax classes, double backward.
 """
 from __future__ import annotations
 
-from typing import Callable, Optional
+from typing import Callable, Optional, Sequence
 
 import torch
 from torch import nn
@@ -297,6 +309,209 @@ class DC_and_topk_loss(nn.Module):
             dc_loss = self.weight_dice * self.dc(net_output, target, loss_mask=mask)
             result = dc_loss if result is None else result + dc_loss
         return net_output.new_zeros((), dtype=torch.float32) if result is None else result
+
+
+# ---------------------------------------------------------------------------------------------------------
+# the region-based loss: sigmoid Dice + BCE on five sums
+# ---------------------------------------------------------------------------------------------------------
+BRATS_REGIONS = ((1, 3), (1, 2, 3), (3,))          # TC, WT, ET over the BraTS labels: convert_labels of the reference's 3_train.py:68-72
+_MAX_REGIONS, _MAX_LABELS = 8, 32
+
+
+def _region_masks(regions, what: str):
+    """((labels of region 0), ...) -> one 32-bit membership mask per region"""
+    try:
+        regions = tuple(tuple(int(l) for l in reg) for reg in regions)
+    except TypeError:
+        raise ValueError(f"{what}: regions must be a sequence of sequences of labels, got {regions!r}") from None
+    if not 1 <= len(regions) <= _MAX_REGIONS:
+        raise ValueError(f"{what}: 1 .. {_MAX_REGIONS} regions, got {len(regions)}")
+    masks = []
+    for reg in regions:
+        if any(not 0 <= l < _MAX_LABELS for l in reg):
+            raise ValueError(f"{what}: the labels of a region must lie in [0, {_MAX_LABELS}), got {reg}")
+        masks.append(sum(1 << l for l in set(reg)))
+    return masks
+
+
+def region_targets(labels: torch.Tensor, regions: Sequence[Sequence[int]] = BRATS_REGIONS) -> torch.Tensor:
+    """label map (B, *spatial) -> float (B, R, *spatial), plane r = 1 where the label belongs to regions[r]: the reference's
+    `convert_labels` (3_train.py:68-72) for any list of regions.  ATen, on whatever device the labels lie."""
+    _region_masks(regions, "region_targets")
+    planes = []
+    for reg in regions:
+        hit = torch.zeros_like(labels, dtype=torch.bool)
+        for l in set(int(l) for l in reg):
+            hit = hit | (labels == l)
+        planes.append(hit)
+    return torch.stack(planes, 1).float()
+
+
+def _region_sums_aten(x, target, masks, ignore_label, ignore_plane):
+    """the five formulas in ATen (CPU tensors): fp32 per voxel, float64 sums"""
+    B, R = x.shape[:2]
+    xf = x.float().reshape(B, R, -1)
+    if masks is not None:
+        lf = target.reshape(B, -1)
+        if lf.is_floating_point():                            # a float label that is no integer is a wrong label, never ignored
+            whole = (lf == lf.floor()) & (lf.abs() < 4.0e18)
+            y = torch.where(whole, lf, torch.full_like(lf, -1)).long()
+        else:
+            whole, y = torch.ones_like(lf, dtype=torch.bool), lf.long()
+        valid = torch.ones_like(y, dtype=torch.bool)
+        if ignore_label is not None:
+            valid = ~(whole & (y == int(ignore_label)))
+        oob = valid & (~whole | (y < 0) | (y >= _MAX_LABELS))
+        bits = torch.tensor(masks, dtype=torch.int64, device=x.device).view(1, R, 1)
+        t = ((bits >> y.clamp(0, _MAX_LABELS - 1).unsqueeze(1)) & 1).to(xf.dtype) * (~oob).unsqueeze(1)
+        poison = torch.where(oob.any(1), float("nan"), 0.0).double()[:, None]
+    else:
+        tf = target.float().reshape(B, target.shape[1], -1)
+        t = tf[:, :R]
+        valid = (1 - tf[:, R]) != 0 if ignore_plane else torch.ones_like(tf[:, 0], dtype=torch.bool)
+        poison = 0.0
+    m = valid.unsqueeze(1).to(xf.dtype)
+    p = torch.sigmoid(xf)
+    bce = torch.clamp(xf, min=0) - xf * t + torch.log1p(torch.exp(-xf.abs()))
+    f64 = torch.float64
+    return ((m * p * t).sum(2, dtype=f64) + poison, (m * p).sum(2, dtype=f64) + poison, (m * t).sum(2, dtype=f64),
+            (m * bce).sum(2, dtype=f64) + poison, valid.sum(1).to(f64))
+
+
+def _refuse_capture(x: torch.Tensor, what: str) -> None:
+    """the runtime is asked only where one is up: without a device the query itself raises"""
+    if (x.is_cuda or torch.cuda.is_initialized()) and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f"{what}: graph capture of the region-based loss is not supported - call it outside the captured region")
+
+
+class _RegionSums(torch.autograd.Function):
+    """segm_region_loss_fwd / segm_region_loss_bwd: differentiable in x through I, P and E"""
+
+    @staticmethod
+    def forward(ctx, x, target, masks, ignore_label, ignore_plane):
+        from . import lib as L, ops_raw
+        I, P, G, E, N = ops_raw.region_loss_fwd(L.get_lib(), x, target, masks, ignore_label, ignore_plane)
+        ctx.save_for_backward(x, target)
+        ctx.mode = (masks, ignore_label, ignore_plane)
+        ctx.mark_non_differentiable(G, N)
+        return I, P, G, E, N
+
+    @staticmethod
+    def backward(ctx, g_i, g_p, _g_g, g_e, _g_n):
+        from . import lib as L, ops_raw
+        x, target = ctx.saved_tensors
+        _refuse_capture(x, "region_sums backward")
+        B, R = x.shape[:2]
+        coefs = [torch.zeros(B, R, dtype=torch.float32, device=x.device) if g is None else g.to(torch.float32) for g in (g_i, g_p, g_e)]
+        masks, ignore_label, ignore_plane = ctx.mode
+        dx = ops_raw.region_loss_bwd(L.get_lib(), x, target, coefs[0], coefs[1], coefs[2], masks, ignore_label, ignore_plane)
+        return dx, None, None, None, None
+
+
+def region_sums(x: torch.Tensor, target: torch.Tensor, regions: Optional[Sequence[Sequence[int]]] = None,
+                ignore_label: Optional[int] = None, use_ignore_label: bool = False, _what: str = "region_sums"):
+    """-> (I, P, G, E, N), float64: with p = sigmoid(x), per (b, r) I = sum m p t, P = sum m p, G = sum m t,
+    E = sum m (max(x, 0) - x t + log1p(exp(-|x|))), and per b N = sum m.  Differentiable in x through I, P and E.
+
+    x: logits (B, R <= 8, *spatial).  `regions` given: target is a label map (B, *spatial) or (B, 1, *spatial), t = [label in
+    regions[r]], m = [label != ignore_label]; a label outside [0, 32) that is not ignored, or a float label that is no integer, gives
+    NaN in that sample's I, P, E.  `regions` None: target holds the planes (B, R, *spatial), used as they are (soft targets work) - or
+    (B, R + 1, *spatial) with `use_ignore_label`, m = ((1 - target[:, -1]) != 0).  Device tensors run on csrc/region_loss.hip (fp32
+    arithmetic on the logits as they lie in memory, any batch / region / row strides; logits without unit stride along the last
+    axis are copied first); CPU tensors take the same formulas in ATen."""
+    from . import lib as L
+    if x.dim() < 3:
+        raise ValueError(f"{_what}: logits must be (B, R, *spatial), got {tuple(x.shape)}")
+    B, R = x.shape[:2]
+    sp = tuple(x.shape[2:])
+    if not 1 <= R <= _MAX_REGIONS:
+        raise ValueError(f"{_what}: 1 .. {_MAX_REGIONS} regions, got {R} channels")
+    plane_like = target.dim() == x.dim() and tuple(target.shape[2:]) == sp and target.shape[0] == B and target.shape[1] in (R, R + 1) \
+        and target.shape[1] != 1
+    masks = None
+    if regions is not None:
+        if plane_like:
+            raise ValueError(f"{_what}: regions= selects the label-map mode, but the target {tuple(target.shape)} holds planes")
+        if use_ignore_label:
+            raise ValueError(f"{_what}: use_ignore_label belongs to a plane target; a label map takes ignore_label=")
+        masks = _region_masks(regions, _what)
+        if len(masks) != R:
+            raise ValueError(f"{_what}: {len(masks)} regions for logits of {R} channels")
+        if target.dim() == x.dim() and target.shape[1] == 1:
+            target = target[:, 0]
+        if tuple(target.shape) != (B,) + sp:
+            raise ValueError(f"{_what}: target must be (B, *spatial) or (B, 1, *spatial), got {tuple(target.shape)} for {tuple(x.shape)}")
+        if target.dtype not in (torch.int64, torch.int16, torch.uint8, torch.float32):
+            target = target.to(torch.float32 if target.is_floating_point() else torch.int64)
+    else:
+        if ignore_label is not None:
+            raise ValueError(f"{_what}: ignore_label belongs to a label map (pass regions=); a plane target takes use_ignore_label")
+        if tuple(target.shape) != (B, R + (1 if use_ignore_label else 0)) + sp:
+            raise ValueError(f"{_what}: target must be (B, *spatial) or (B, 1, *spatial) with regions=, (B, R, *spatial), or "
+                             f"(B, R + 1, *spatial) with use_ignore_label; got {tuple(target.shape)} for {tuple(x.shape)}")
+        if target.dtype == torch.bool:
+            target = target.contiguous().view(torch.uint8)
+        elif target.dtype not in (torch.uint8, torch.float32):
+            target = target.float()
+    if not L.on_device(x):
+        return _region_sums_aten(x, target, masks, ignore_label, bool(use_ignore_label))
+    _refuse_capture(x, _what)
+    from . import ops_raw
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{_what}: logits of {x.dtype} have no kernel (fp32, fp16, bf16)")
+    if not ops_raw.region_loss_layout_supported(x):
+        x = x.contiguous()
+    return _RegionSums.apply(x, target.contiguous(), masks, None if ignore_label is None else int(ignore_label), bool(use_ignore_label))
+
+
+class DC_and_BCE_loss(nn.Module):
+    """reference compound_losses.py:60-100 on `region_sums`, plus `regions` / `ignore_label`, which select the label-map mode.
+
+    Plane mode (the reference's): target (B, R, ...) one-hot or soft, or (B, R + 1, ...) with `use_ignore_label`.  Label mode:
+    `regions=BRATS_REGIONS` (or any sets of labels), target (B, ...) or (B, 1, ...), `ignore_label` optional.  The Dice term is
+    `dice_class(...).from_sums(I, P, G)` - batch_dice, do_bg (drops region 0, as the reference's x[:, 1:]), smooth, clip_tp, ddp and the
+    clip of the denominator are that class' arithmetic.  The BCE term is E.sum() / (B R V) without a mask and
+    E.sum() / clip(N.sum(), 1e-8) with one: the reference divides the masked sum over all regions by the number of valid voxels
+    (compound_losses.py:96), not by R times that number."""
+
+    def __init__(self, bce_kwargs, soft_dice_kwargs, weight_ce=1, weight_dice=1, use_ignore_label: bool = False,
+                 dice_class=MemoryEfficientSoftDiceLoss, regions: Optional[Sequence[Sequence[int]]] = None,
+                 ignore_label: Optional[int] = None):
+        super().__init__()
+        bce_kwargs = dict(bce_kwargs)
+        if bce_kwargs.get("weight") is not None or bce_kwargs.get("pos_weight") is not None:
+            raise NotImplementedError("DC_and_BCE_loss: weight and pos_weight are not supported (the kernel has none)")
+        if bce_kwargs.get("reduction", "mean") != "mean" or bce_kwargs.get("size_average") is not None or \
+                bce_kwargs.get("reduce") is not None:
+            raise NotImplementedError("DC_and_BCE_loss: only reduction='mean' is supported (use_ignore_label masks the sum itself)")
+        if dice_class not in (SoftDiceLoss, MemoryEfficientSoftDiceLoss):
+            raise NotImplementedError("DC_and_BCE_loss: dice_class must be SoftDiceLoss or MemoryEfficientSoftDiceLoss of this module")
+        if regions is not None and use_ignore_label:
+            raise ValueError("DC_and_BCE_loss: use_ignore_label belongs to a plane target; with regions= pass ignore_label=")
+        if regions is None and ignore_label is not None:
+            raise ValueError("DC_and_BCE_loss: ignore_label belongs to the label-map mode; pass regions= as well")
+        self.weight_dice, self.weight_ce, self.use_ignore_label = weight_dice, weight_ce, use_ignore_label
+        self.regions = None if regions is None else tuple(tuple(int(l) for l in reg) for reg in regions)
+        if self.regions is not None:
+            _region_masks(self.regions, "DC_and_BCE_loss")
+        self.ignore_label = ignore_label
+        # kept under the reference's attribute name: it validates bce_kwargs; forward() takes the BCE term from the sums
+        self.ce = nn.BCEWithLogitsLoss(**bce_kwargs)
+        self.dc = dice_class(apply_nonlin=torch.sigmoid, **soft_dice_kwargs)
+
+    def forward(self, net_output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        intersect, sum_pred, sum_gt, bce_sum, count = region_sums(net_output, target, self.regions, self.ignore_label,
+                                                                  self.use_ignore_label, _what="DC_and_BCE_loss")
+        result = intersect.new_zeros(())                       # a tensor also when both weights are 0
+        if self.weight_ce != 0:
+            if self.use_ignore_label or self.ignore_label is not None:
+                ce_loss = bce_sum.sum() / torch.clip(count.sum(), min=1e-8)
+            else:
+                ce_loss = bce_sum.sum() / net_output.numel()
+            result = self.weight_ce * ce_loss
+        if self.weight_dice != 0:
+            result = result + self.weight_dice * self.dc.from_sums(intersect, sum_pred, sum_gt)
+        return result.to(torch.float32)
 
 
 class DeepSupervisionWrapper(nn.Module):

@@ -1144,6 +1144,138 @@ def cross_entropy_map_bwd(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Te
     return dlogits
 
 
+def _region_layout(logits: torch.Tensor):
+    """the spatial axes of (B, R, *spatial) logits as (z, y, x) - x the last axis, y the one before, z whatever lies in front, which
+    one stride must serve -> (Z, Y, X, stride_z, stride_y), or None where the strides do not allow it"""
+    sp, st = tuple(logits.shape[2:]), logits.stride()
+    X = sp[-1]
+    Y = sp[-2] if len(sp) >= 2 else 1
+    Z = 1
+    for s in sp[:-2]:
+        Z *= s
+    if X != 1 and st[-1] != 1:
+        return None
+    sy = st[-2] if len(sp) >= 2 and Y != 1 else X
+    lead = [(sp[i], st[2 + i]) for i in range(len(sp) - 2) if sp[i] != 1]
+    sz = X * Y
+    if lead:
+        sz = lead[-1][1]
+        for (_, s_out), (n_in, s_in) in zip(lead[:-1], lead[1:]):
+            if s_out != s_in * n_in:
+                return None
+    return Z, Y, X, sz, sy
+
+
+def region_loss_layout_supported(logits: torch.Tensor) -> bool:
+    """whether the region-loss entries take these logits as they lie in memory (a caller may pass a dense copy otherwise)"""
+    return logits.dim() >= 3 and logits.numel() > 0 and _region_layout(logits) is not None
+
+
+def _region_args(logits: torch.Tensor, target: torch.Tensor, masks, ignore_label, ignore_plane: bool, what: str):
+    """the checks and the argument struct the two region-loss entries share -> (args, target kept alive)"""
+    if not isinstance(logits, torch.Tensor) or not isinstance(target, torch.Tensor):
+        raise RuntimeError(f"{what}: logits and target must be tensors")
+    if logits.dim() < 3 or logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise RuntimeError(f"{what}: logits (B, R, *spatial) fp32 / fp16 / bf16")
+    B, R = logits.shape[:2]
+    sp = tuple(logits.shape[2:])
+    if not 1 <= R <= L.REGION_MAX_REGIONS:
+        raise RuntimeError(f"{what}: 1 .. {L.REGION_MAX_REGIONS} regions, got {R}")
+    if logits.numel() == 0:
+        raise RuntimeError(f"{what}: empty logits {tuple(logits.shape)}")
+    if target.device != logits.device:
+        raise RuntimeError(f"{what}: the target lies on {target.device}, the logits on {logits.device}")
+    V = 1
+    for s in sp:
+        V *= s
+    if V >= 1 << 31:
+        raise RuntimeError(f"{what}: {V} voxels per sample, fewer than 2^31 are supported")
+    layout = _region_layout(logits)
+    if layout is None:
+        raise RuntimeError(f"{what}: the logits need unit stride along the last axis and spatial axes in front of the last two "
+                           f"that collapse into one stride, got strides {logits.stride()} for {tuple(logits.shape)}")
+    Z, Y, X, sz, sy = layout
+    st = logits.stride()
+    a = L.RegionLossArgs()
+    a.batch, a.regions, a.dtype = B, R, L.dtype_code(logits)
+    a.depth, a.height, a.width = Z, Y, X
+    a.stride_b, a.stride_r, a.stride_z, a.stride_y, a.stride_x = st[0], st[1], sz, sy, 1
+    if masks is not None:
+        if ignore_plane:
+            raise RuntimeError(f"{what}: an ignore plane belongs to a plane target, not to a label map")
+        masks = [int(m) for m in masks]
+        if len(masks) != R or any(not 0 <= m < 1 << 32 for m in masks):
+            raise RuntimeError(f"{what}: {R} membership masks of 32 bits, got {masks}")
+        if tuple(target.shape) != (B,) + sp or target.dtype not in L.REGION_LABELS:
+            raise RuntimeError(f"{what}: a label map {(B,) + sp} of int64 / int16 / uint8 / float32, got {tuple(target.shape)} "
+                               f"{target.dtype}")
+        a.target_kind = L.REGION_LABELS[target.dtype]
+        for r, m in enumerate(masks):
+            a.masks[r] = m
+        if ignore_label is not None:
+            if not -(1 << 63) <= int(ignore_label) < 1 << 63:
+                raise RuntimeError(f"{what}: ignore_label {ignore_label} is no 64-bit integer")
+            a.has_ignore, a.ignore_label = 1, int(ignore_label)
+    else:
+        if ignore_label is not None:
+            raise RuntimeError(f"{what}: ignore_label belongs to a label map (pass masks), a plane target takes ignore_plane")
+        if target.dtype == torch.bool:
+            target = target.contiguous().view(torch.uint8)
+        planes = R + (1 if ignore_plane else 0)
+        if tuple(target.shape) != (B, planes) + sp or target.dtype not in L.REGION_PLANES:
+            raise RuntimeError(f"{what}: a plane target {(B, planes) + sp} of uint8 / bool / float32, got {tuple(target.shape)} "
+                               f"{target.dtype}")
+        a.target_kind, a.ignore_plane = L.REGION_PLANES[target.dtype], int(bool(ignore_plane))
+    target = target.contiguous()
+    a.logits, a.target = logits.data_ptr(), target.data_ptr()
+    a.stream = L.stream_handle(logits)
+    return a, target
+
+
+def region_loss_fwd(lib: L.SegmLib, logits: torch.Tensor, target: torch.Tensor, masks=None, ignore_label: int = None,
+                    ignore_plane: bool = False, workspace: torch.Tensor = None):
+    """The sums of the region-based loss, float64 on the device: -> (I, P, G, E) of shape (B, R) and N of shape (B).  With
+    p = sigmoid(logits): I = sum m p t, P = sum m p, G = sum m t, E = sum m (max(x, 0) - x t + log1p(exp(-|x|))), N = sum m.
+    logits (B, R <= 8, *spatial) fp32 / fp16 / bf16, unit stride along the last axis, any batch / region / row strides.
+    `masks` given: target is a label map (B, *spatial) int64 / int16 / uint8 / float32 and t = (masks[r] >> label) & 1; a label equal
+    to `ignore_label` has m = 0; any other label outside [0, 32) gives NaN in its sample's I, P, E.  `masks` None: target holds the
+    planes (B, R, *spatial) - or (B, R + 1, *spatial) with `ignore_plane`, m = ((1 - last) != 0) - of uint8 / bool / float32."""
+    a, target = _region_args(logits, target, masks, ignore_label, ignore_plane, "region_loss_fwd")
+    B, R = logits.shape[:2]
+    nbytes = lib.dll.segm_region_loss_workspace_bytes(B, R, a.depth * a.height * a.width)
+    if nbytes == 0:
+        raise RuntimeError(f"region_loss_fwd: the shape {tuple(logits.shape)} is out of range")
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != logits.device or not workspace.is_contiguous():
+        raise RuntimeError("region_loss_fwd: the workspace must be a contiguous tensor on the logits' device")
+    sums = torch.empty(4 * B * R + B, dtype=torch.float64, device=logits.device)
+    a.sums = sums.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    lib.check(lib.dll.segm_region_loss_fwd(a), "region_loss_fwd")
+    four = sums[:4 * B * R].view(4, B, R)
+    return four[0], four[1], four[2], four[3], sums[4 * B * R:]
+
+
+def region_loss_bwd(lib: L.SegmLib, logits: torch.Tensor, target: torch.Tensor, g_i: torch.Tensor, g_p: torch.Tensor,
+                    g_e: torch.Tensor, masks=None, ignore_label: int = None, ignore_plane: bool = False) -> torch.Tensor:
+    """-> dlogits = m (p (1 - p) (g_i t + g_p) + g_e (p - t)), dense, in the logits' dtype and shape; exactly 0 where m = 0, NaN at a
+    wrong label.  g_i, g_p, g_e: fp32 (B, R) on the logits' device, the gradients of the loss by I, P and E of `region_loss_fwd`;
+    the other arguments as there."""
+    a, target = _region_args(logits, target, masks, ignore_label, ignore_plane, "region_loss_bwd")
+    B, R = logits.shape[:2]
+    coefs = []
+    for name, g in (("g_i", g_i), ("g_p", g_p), ("g_e", g_e)):
+        if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != (B, R) or g.device != logits.device:
+            raise RuntimeError(f"region_loss_bwd: {name} must be fp32 {(B, R)} on the logits' device")
+        coefs.append(g.contiguous())
+    a.g_i, a.g_p, a.g_e = (g.data_ptr() for g in coefs)
+    dlogits = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+    a.dlogits = dlogits.data_ptr()
+    lib.check(lib.dll.segm_region_loss_bwd(a), "region_loss_bwd")
+    return dlogits
+
+
 # ---------------------------------------------------------------------------------------------------------
 # single-token decode steps
 # ---------------------------------------------------------------------------------------------------------
