@@ -1276,6 +1276,63 @@ int segm_region_loss_fwd(const segm_region_loss_args* args);
 int segm_region_loss_bwd(const segm_region_loss_args* args);
 
 /* ------------------------------------------------------------------------------------------------
+ * Softmax Dice + cross entropy: the sums behind nnU-Net's default loss and their gradient (additive to ABI 10; csrc/dice_ce.hip).
+ * Replaces what the reference's Dice classes (light_training/loss/dice.py:9-116) and DC_and_CE_loss
+ * (light_training/loss/compound_losses.py:8-57) run over the volume: the softmax, the one-hot target, the products with it and with
+ * the loss mask, the reductions over the spatial axes, RobustCrossEntropyLoss, and the backward of all of them.  What follows the
+ * sums (batch_dice, do_bg, smooth, clip_tp, the means, the weights) is arithmetic on (batch, classes) tensors and stays with the
+ * caller.
+ *
+ * With p = softmax_c(x), the label y(b, v) and the validity m(b, v), per (b, c)
+ *     I = sum_v m p_c [y = c]     P = sum_v m p_c     G = sum_v m [y = c]
+ * and per b     CE = sum_v m (logsumexp_c(x) - x_y)     N = sum_v m.
+ *
+ * logits: (batch, classes, depth, height, width), classes in [1, SEGM_SOFTMAX_DICE_MAX_CLASSES] (the limit of
+ * segm_cross_entropy_map), fp32 / fp16 / bf16 (arithmetic in fp32, every term added in fp64), element strides for batch, class, z
+ * and y, stride_x == 1 (SEGM_E_SHAPE otherwise), aligned to its element size; depth * height * width < 2^31.  A caller with fewer
+ * spatial axes passes 1 for the missing ones.
+ * labels: (batch, depth, height, width), dense, label_kind one of SEGM_REGION_LABELS_I64 / _I16 / _U8 / _F32.  With has_ignore a
+ * label equal to ignore_label (any value; compared before the range check) has m = 0.  mask: optional, uint8, dense, the labels'
+ * shape; m = 0 where it is 0.  A label with m = 1 outside [0, classes), or a float label that is no integer (NaN included), puts NaN
+ * into that sample's I, P and CE (a wrong label stays loud) and into its voxel of dlogits; the other samples stay finite.
+ * G and N are exact; I is exactly 0 for a class that never occurs.
+ * Per-workgroup partial rows in the workspace, added by one workgroup per sample in a fixed order, all in fp64; no floating-point
+ * atomic: two calls on the same tensors are bit-equal.  The aligned route (16-byte packets of logits) and the per-voxel route
+ * compute every voxel's terms alike but add them in another order: no bit-equality between differently aligned views.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_SOFTMAX_DICE_MAX_CLASSES 16
+
+typedef struct segm_softmax_dice_args {
+    int32_t batch, classes, dtype, label_kind;
+    int32_t depth, height, width;
+    int32_t has_ignore;            /* whether ignore_label counts */
+    int64_t ignore_label;
+    int64_t stride_b, stride_c, stride_z, stride_y, stride_x;      /* of logits, in elements; stride_x must be 1 */
+    const void* logits;
+    const void* labels;
+    const uint8_t* mask;           /* optional */
+    double* sums;                  /* fwd: out, fp64 [I (batch, classes) | P | G | CE (batch) | N (batch)] */
+    const float* g_i;              /* bwd: (batch, classes) fp32, dense, in device memory: d loss / d I, / d P */
+    const float* g_p;
+    const float* g_ce;             /* bwd: (batch) fp32: d loss / d CE */
+    void* dlogits;                 /* bwd: out, (batch, classes, depth, height, width) dense, the logits' dtype */
+    void* workspace;     size_t workspace_bytes;                    /* fwd only */
+    void* stream;
+} segm_softmax_dice_args;
+
+/* 0 for a shape out of range.  Workspace NULL, misaligned (8 bytes) or smaller than this: SEGM_E_WORKSPACE. */
+size_t segm_softmax_dice_workspace_bytes(int32_t batch, int32_t classes, int64_t voxels);
+
+/* The five sums (dice.py:9-116 and compound_losses.py:8-57 up to the sums).  Two launches - the streaming kernel and a
+ * one-workgroup-per-sample kernel that adds the partial rows - nothing is read back. */
+int segm_softmax_dice_fwd(const segm_softmax_dice_args* args);
+
+/* dlogits_j = m (p_j (a_j - S) + g_ce (p_j - [j = y])) with a_c = g_i[c] [y = c] + g_p[c] and S = sum_c p_c a_c; exactly 0 where
+ * m = 0; the softmax is recomputed (the backward of dice.py:9-116 and compound_losses.py:8-57 given the gradients of the loss by the
+ * sums).  One launch, nothing is read back. */
+int segm_softmax_dice_bwd(const segm_softmax_dice_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * Resampling a case to the target spacing (additive to ABI 10; csrc/resample.hip).
  * Replaces the reference's resample_data_or_seg without a separate z axis (light_training/preprocessing/resampling/
  * default_resampling.py:126-217 as default_preprocessor.py:187-201 calls it): skimage's resize(order 3 or 1, mode='edge',

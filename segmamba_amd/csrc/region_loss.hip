@@ -22,7 +22,7 @@
 #include <math.h>
 #include <string.h>
 
-#include "segm_device.h"
+#include "loss_common.h"
 
 namespace segm {
 
@@ -49,14 +49,7 @@ struct RlDev {
 };
 
 // ---- the per-voxel arithmetic: one function for every route ---------------------------------------------------------------------------
-// The library is built with -ffp-contract=fast, under which the backend may fuse a product into a following sum whatever a pragma
-// says, and two instantiations need not fuse alike.  RL_ROUND(x) makes x a value the compiler has to form as written (an empty asm
-// that reads and writes the register, no memory clobber), so a product that feeds a sum is rounded on its own in every route.
-#ifdef SEGM_EMU
-#define RL_ROUND(x) ((void)0)
-#else
-#define RL_ROUND(x) asm("" : "+v"(x))
-#endif
+// RL_ROUND (loss_common.h): a product that feeds a sum is rounded on its own in every route.
 
 struct RlTerms { float p, pt, e; };
 
@@ -106,14 +99,6 @@ __device__ __forceinline__ int64_t rl_offset(const RlDev& P, int64_t v) {
     const uint32_t row = (uint32_t)v / (uint32_t)P.X, col = (uint32_t)v - row * (uint32_t)P.X;
     const uint32_t z = row / (uint32_t)P.Y, y = row - z * (uint32_t)P.Y;
     return (int64_t)z * P.sz + (int64_t)y * P.sy + (int64_t)col;
-}
-
-// N elements of the dense target from element index i; a packet starts at a multiple of N elements of a 16-byte aligned base
-template <typename S, int N>
-__device__ __forceinline__ void rl_load(const void* base, int64_t i, S raw[N]) {
-    const S* p = reinterpret_cast<const S*>(base) + i;
-    if (N == 1) raw[0] = p[0];
-    else memcpy(raw, __builtin_assume_aligned(p, (N * sizeof(S) < 16 ? N * sizeof(S) : 16)), N * sizeof(S));
 }
 
 // the labels of a packet: lab in [0, 32) (0 where it does not count), m = the voxel counts, bit k of bad = voxel k has a wrong label
@@ -196,11 +181,6 @@ __device__ __forceinline__ void rl_packet_target(const RlDev& P, int b, int r, u
             rl_load<float, N>(P.target, j, t);
         }
     }
-}
-
-__device__ __forceinline__ double rl_wave_sum(double v) {
-    for (int off = kWave / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
 }
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------------------

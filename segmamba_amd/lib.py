@@ -304,6 +304,7 @@ EXPORTS = (
     "segm_crop_clip_normalize", "segm_fg_workspace_bytes", "segm_fg_count", "segm_fg_order_stats", "segm_fg_gather",
     "segm_cross_entropy_map", "segm_cross_entropy_map_bwd", "segm_topk_select", "segm_topk_select_workspace_bytes",
     "segm_region_loss_workspace_bytes", "segm_region_loss_fwd", "segm_region_loss_bwd",
+    "segm_softmax_dice_workspace_bytes", "segm_softmax_dice_fwd", "segm_softmax_dice_bwd",
     "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
     "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
     "segm_gauss_blur",
@@ -468,6 +469,20 @@ class RegionLossArgs(C.Structure):
                 ("masks", C.c_uint32 * REGION_MAX_REGIONS),
                 ("logits", C.c_void_p), ("target", C.c_void_p), ("sums", C.c_void_p),
                 ("g_i", C.c_void_p), ("g_p", C.c_void_p), ("g_e", C.c_void_p), ("dlogits", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+SOFTMAX_DICE_MAX_CLASSES = 16                                                  # SEGM_SOFTMAX_DICE_MAX_CLASSES
+
+
+class SoftmaxDiceArgs(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("classes", C.c_int32), ("dtype", C.c_int32), ("label_kind", C.c_int32),
+                ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("has_ignore", C.c_int32),
+                ("ignore_label", C.c_int64),
+                ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_x", C.c_int64),
+                ("logits", C.c_void_p), ("labels", C.c_void_p), ("mask", C.c_void_p), ("sums", C.c_void_p),
+                ("g_i", C.c_void_p), ("g_p", C.c_void_p), ("g_ce", C.c_void_p), ("dlogits", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
@@ -644,6 +659,9 @@ class SegmLib:
         sig("segm_region_loss_workspace_bytes", [C.c_int32, C.c_int32, C.c_int64], C.c_size_t)
         sig("segm_region_loss_fwd", [C.POINTER(RegionLossArgs)], C.c_int)
         sig("segm_region_loss_bwd", [C.POINTER(RegionLossArgs)], C.c_int)
+        sig("segm_softmax_dice_workspace_bytes", [C.c_int32, C.c_int32, C.c_int64], C.c_size_t)
+        sig("segm_softmax_dice_fwd", [C.POINTER(SoftmaxDiceArgs)], C.c_int)
+        sig("segm_softmax_dice_bwd", [C.POINTER(SoftmaxDiceArgs)], C.c_int)
         sig("segm_zoom", [C.POINTER(ZoomArgs)], C.c_int)
         sig("segm_zoom_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_zoom_labels", [C.POINTER(ZoomLabelsArgs)], C.c_int)

@@ -8,11 +8,16 @@ sigmoid Dice + BCE under the reference's names.
     P = sum m p_c, G = sum m [y = c] and, per b, the cross-entropy sum and the number of valid voxels.  SoftDiceLoss' tp, fp, fn are
     I, P - I, G - I; what follows the sums (batch_dice, do_bg, smooth, clip_tp, the clip of the denominator, the mean, the weights) is
     arithmetic on (B, C) tensors;
-  * these softmax sums are computed in ATen for CPU tensors only.  The library has no kernel for them, and no ATen fall-back on the
-    device: everything that needs them refuses device tensors with NotImplementedError;
+  * `dice_ce_sums` computes these softmax sums in ATen, for CPU tensors only, and has no ATen fall-back on the device: by default
+    everything that needs them refuses device tensors with NotImplementedError;
+  * `softmax_dice_sums` is the same five sums on the device, from csrc/dice_ce.hip (one pass over the logits, the labels and the mask
+    for all classes, fp64 sums in a fixed order, a one-launch backward that recomputes the softmax; CPU tensors take `dice_ce_sums`'
+    ATen formulas).  The opt-in keyword `device_sums=True` of `SoftDiceLoss`, `MemoryEfficientSoftDiceLoss`, `DC_and_CE_loss` and
+    `DC_and_topk_loss` sends device tensors under `apply_nonlin=softmax_helper_dim1` there; the loss is then returned as float32.
+    The default `device_sums=False` keeps every refusal;
   * on the device run `RobustCrossEntropyLoss` (on `train_ops.cross_entropy`), `TopKLoss` (on `train_ops.topk_cross_entropy`: the
-    per-voxel map, an exact radix selection, a per-voxel backward - csrc/topk_ce.hip) and `DC_and_topk_loss` with `weight_dice=0`,
-    which never asks for the sums;
+    per-voxel map, an exact radix selection, a per-voxel backward - csrc/topk_ce.hip) and `DC_and_topk_loss` - with `weight_dice=0`,
+    which never asks for the sums, or with `device_sums=True`, which takes them from `softmax_dice_sums`;
   * `DC_and_BCE_loss` (compound_losses.py:60-100), the region-based loss - one sigmoid output per region, Dice on the sigmoids plus
     BCEWithLogitsLoss - runs on the device on `region_sums`: per (b, r) I = sum m p t, P = sum m p, G = sum m t,
     E = sum m (max(x, 0) - x t + log1p(exp(-|x|))) and per b N = sum m, from csrc/region_loss.hip (one pass over the logits and the
@@ -28,8 +33,10 @@ for the CE term (the reference's `num_fg > 0` rule; the top-k term needs no rule
 indexing error; `TopKLoss` raises ValueError where k selects no voxel (the reference returns the NaN of an empty mean), and among
 voxels tied with the k-th largest loss each gets an equal share of the gradient where `torch.topk` picks some of them (same value).
 `DC_and_BCE_loss`: in label mode a label outside [0, 32) that is not ignored, or a float label that is no integer, gives NaN; the
-sums are float64 and the loss is returned as float32; `weight`, `pos_weight` and reductions other than the mean are refused; while a
-graph is being captured the device path raises RuntimeError before any launch (capture of this loss is unsupported).
+sums are float64 and the loss is returned as float32; `weight`, `pos_weight` and reductions other than the mean are refused.
+While a graph is being captured the device paths of `region_sums` and `softmax_dice_sums` raise RuntimeError before any launch,
+forward and backward: capture of these losses is unsupported (a captured loss forward + backward once ended in a segmentation fault
+whose cause was never found, and nothing here captures one).
 Not here: AutoDeepSupervision, class weights, label smoothing, one-hot targets for the softmax classes, double backward.
 """
 from __future__ import annotations
@@ -121,8 +128,65 @@ def dice_ce_sums(x: torch.Tensor, target: torch.Tensor, loss_mask: Optional[torc
     mask = _mask_of(x, loss_mask, _what)
     if not L.on_device(x):
         return _sums_aten(x, labels, mask, ignore_label, apply_nonlin)
-    raise NotImplementedError(f"{_what}: the library has no kernel for the Dice sums and no ATen fall-back on the device - use CPU "
-                              "tensors, or train_ops.cross_entropy / RobustCrossEntropyLoss, which run on the library's kernel")
+    raise NotImplementedError(f"{_what}: dice_ce_sums has no ATen fall-back on the device - use CPU tensors, pass device_sums=True "
+                              "(softmax_dice_sums, the library's kernel for the sums under the softmax), or "
+                              "train_ops.cross_entropy / RobustCrossEntropyLoss")
+
+
+class _SoftmaxDiceSums(torch.autograd.Function):
+    """segm_softmax_dice_fwd / segm_softmax_dice_bwd: differentiable in x through I, P and CE"""
+
+    @staticmethod
+    def forward(ctx, x, labels, mask, ignore_label):
+        from . import lib as L, ops_raw
+        I, P, G, CE, N = ops_raw.softmax_dice_fwd(L.get_lib(), x, labels, mask, ignore_label)
+        ctx.save_for_backward(x, labels, *(() if mask is None else (mask,)))
+        ctx.ignore_label = ignore_label
+        ctx.mark_non_differentiable(G, N)
+        return I, P, G, CE, N
+
+    @staticmethod
+    def backward(ctx, g_i, g_p, _g_g, g_ce, _g_n):
+        from . import lib as L, ops_raw
+        x, labels, *rest = ctx.saved_tensors
+        _refuse_capture(x, "softmax_dice_sums backward")
+        B, Cc = x.shape[:2]
+        coefs = [torch.zeros(shape, dtype=torch.float32, device=x.device) if g is None else g.to(torch.float32)
+                 for g, shape in ((g_i, (B, Cc)), (g_p, (B, Cc)), (g_ce, (B,)))]
+        dx = ops_raw.softmax_dice_bwd(L.get_lib(), x, labels, coefs[0], coefs[1], coefs[2], rest[0] if rest else None, ctx.ignore_label)
+        return dx, None, None, None
+
+
+def softmax_dice_sums(x: torch.Tensor, target: torch.Tensor, loss_mask: Optional[torch.Tensor] = None,
+                      ignore_label: Optional[int] = None, _what: str = "softmax_dice_sums"):
+    """-> (I (B, C), P (B, C), G (B, C), CE (B), N (B)): with p = softmax(x, 1), I = sum m p_c [y = c], P = sum m p_c,
+    G = sum m [y = c], CE = sum m (logsumexp(x) - x_y), N = sum m, where m = 0 at a label equal to `ignore_label` and where
+    `loss_mask` is 0.  Differentiable in x through I, P and CE.
+
+    x: logits (B, C <= 16, *spatial); target: a label map (B, 1, *spatial) or (B, *spatial), float or integer; loss_mask: bool, uint8
+    or 0 / 1 float of either shape.  A label outside [0, C) that counts, or a float label that is no integer, gives NaN in its
+    sample's I, P, CE.  Device tensors run on csrc/dice_ce.hip and give float64 sums (fp32 arithmetic on the logits as they lie in
+    memory, any batch / class / row strides; logits without unit stride along the last axis are copied first); CPU tensors take
+    `dice_ce_sums`' formulas in ATen."""
+    from . import lib as L
+    if x.dim() < 3:
+        raise ValueError(f"{_what}: logits must be (B, C, *spatial), got {tuple(x.shape)}")
+    on_device = L.on_device(x)
+    if on_device:
+        _refuse_capture(x, _what)                             # before anything is launched, the conversions of the target included
+    labels = _labels_of(x, target, _what)
+    mask = _mask_of(x, loss_mask, _what)
+    if not on_device:
+        return _sums_aten(x, labels, mask, ignore_label, softmax_helper_dim1)
+    from . import ops_raw
+    if not 1 <= x.shape[1] <= L.SOFTMAX_DICE_MAX_CLASSES:
+        raise NotImplementedError(f"{_what}: 1 .. {L.SOFTMAX_DICE_MAX_CLASSES} classes have a kernel, got {x.shape[1]}")
+    if x.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise NotImplementedError(f"{_what}: logits of {x.dtype} have no kernel (fp32, fp16, bf16)")
+    if not ops_raw.softmax_dice_layout_supported(x):
+        x = x.contiguous()
+    return _SoftmaxDiceSums.apply(x, labels.contiguous(), None if mask is None else mask.contiguous(),
+                                  None if ignore_label is None else int(ignore_label))
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -157,11 +221,19 @@ def _sum_over_ranks(t: torch.Tensor) -> torch.Tensor:
 # the reference's classes
 # ---------------------------------------------------------------------------------------------------------
 class _DiceBase(nn.Module):
-    def __init__(self, apply_nonlin, batch_dice, do_bg, smooth, ddp):
+    def __init__(self, apply_nonlin, batch_dice, do_bg, smooth, ddp, device_sums=False):
         super().__init__()
         self.apply_nonlin, self.batch_dice, self.do_bg, self.smooth, self.ddp = apply_nonlin, batch_dice, do_bg, smooth, ddp
+        self.device_sums = bool(device_sums)
 
     def forward(self, x, y, loss_mask=None):
+        from . import lib as L
+        if self.device_sums and L.on_device(x):
+            if self.apply_nonlin is not softmax_helper_dim1:
+                raise NotImplementedError(f"{type(self).__name__}: device_sums=True serves apply_nonlin=softmax_helper_dim1 only - the "
+                                          "kernel computes the softmax itself")
+            intersect, sum_pred, sum_gt, _, _ = softmax_dice_sums(x, y, loss_mask, None, _what=type(self).__name__)
+            return self.from_sums(intersect, sum_pred, sum_gt).to(torch.float32)
         intersect, sum_pred, sum_gt, _, _ = dice_ce_sums(x, y, loss_mask, None, self.apply_nonlin, _what=type(self).__name__)
         return self.from_sums(intersect, sum_pred, sum_gt)
 
@@ -180,11 +252,12 @@ class _DiceBase(nn.Module):
 
 
 class SoftDiceLoss(_DiceBase):
-    """reference dice.py:9-56 on the three sums: tp = I, fp = P - I, fn = G - I"""
+    """reference dice.py:9-56 on the three sums: tp = I, fp = P - I, fn = G - I.  `device_sums=True`: device tensors under the softmax
+    take the sums from `softmax_dice_sums` and the loss is float32; the default refuses them."""
 
     def __init__(self, apply_nonlin: Callable = None, batch_dice: bool = False, do_bg: bool = True, smooth: float = 1.,
-                 ddp: bool = True, clip_tp: float = None):
-        super().__init__(apply_nonlin, batch_dice, do_bg, smooth, ddp)
+                 ddp: bool = True, clip_tp: float = None, device_sums: bool = False):
+        super().__init__(apply_nonlin, batch_dice, do_bg, smooth, ddp, device_sums)
         self.clip_tp = clip_tp
 
     def from_sums(self, intersect, sum_pred, sum_gt):
@@ -198,11 +271,11 @@ class SoftDiceLoss(_DiceBase):
 
 
 class MemoryEfficientSoftDiceLoss(_DiceBase):
-    """reference dice.py:58-116"""
+    """reference dice.py:58-116; `device_sums` as in `SoftDiceLoss`"""
 
     def __init__(self, apply_nonlin: Callable = None, batch_dice: bool = False, do_bg: bool = True, smooth: float = 1.,
-                 ddp: bool = True):
-        super().__init__(apply_nonlin, batch_dice, do_bg, smooth, ddp)
+                 ddp: bool = True, device_sums: bool = False):
+        super().__init__(apply_nonlin, batch_dice, do_bg, smooth, ddp, device_sums)
 
     def from_sums(self, intersect, sum_pred, sum_gt):
         intersect, sum_pred, sum_gt = self._reduced(intersect, sum_pred, sum_gt)
@@ -254,10 +327,13 @@ class TopKLoss(nn.Module):
 
 class DC_and_CE_loss(nn.Module):
     """reference compound_losses.py:8-57.  Both terms come from the same five sums; `ignore_label` goes into them instead of a mask and
-    a cloned target, and the CE term is ce_sum / max(count, 1): 0 when every voxel is ignored."""
+    a cloned target, and the CE term is ce_sum / max(count, 1): 0 when every voxel is ignored.  `device_sums=True`: device tensors take
+    the sums from `softmax_dice_sums` (csrc/dice_ce.hip) and the loss is float32; the default refuses them."""
 
-    def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None, dice_class=SoftDiceLoss):
+    def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None, dice_class=SoftDiceLoss,
+                 device_sums: bool = False):
         super().__init__()
+        self.device_sums = bool(device_sums)
         ce_kwargs = dict(ce_kwargs)
         if ignore_label is not None:
             ce_kwargs["ignore_index"] = ignore_label
@@ -272,31 +348,43 @@ class DC_and_CE_loss(nn.Module):
     def forward(self, net_output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
         if self.ignore_label is not None and target.dim() == net_output.dim() and target.shape[1] != 1:
             raise NotImplementedError("DC_and_CE_loss: ignore_label needs a label map (B, 1, ...), not a one-hot target")
-        intersect, sum_pred, sum_gt, ce_sum, count = dice_ce_sums(net_output, target, None, self.ce.ignore_index, softmax_helper_dim1,
-                                                                  _what="DC_and_CE_loss")
+        from . import lib as L
+        on_kernel = self.device_sums and L.on_device(net_output)
+        if on_kernel:
+            intersect, sum_pred, sum_gt, ce_sum, count = softmax_dice_sums(net_output, target, None, self.ce.ignore_index,
+                                                                           _what="DC_and_CE_loss")
+        else:
+            intersect, sum_pred, sum_gt, ce_sum, count = dice_ce_sums(net_output, target, None, self.ce.ignore_index,
+                                                                      softmax_helper_dim1, _what="DC_and_CE_loss")
         result = intersect.new_zeros(())                       # a tensor also when both weights are 0
         if self.weight_ce != 0:
             result = self.weight_ce * (ce_sum.sum() / count.sum().clamp(min=1))
         if self.weight_dice != 0:
             result = result + self.weight_dice * self.dc.from_sums(intersect, sum_pred, sum_gt)
-        return result
+        return result.to(torch.float32) if on_kernel else result
 
 
 class DC_and_topk_loss(nn.Module):
-    """reference compound_losses.py:103-151.  The Dice term is `SoftDiceLoss` on the sums (CPU tensors; it refuses device tensors),
+    """reference compound_losses.py:103-151.  The Dice term is `SoftDiceLoss` on the sums (CPU tensors; by default it refuses device tensors),
     with the ignored voxels masked out as the reference does; it is skipped when `weight_dice == 0`, which then runs on the device.
-    The reference's `num_fg > 0` rule needs no readback: if every voxel is ignored the map is all zeros and the top-k mean is 0."""
+    The reference's `num_fg > 0` rule needs no readback: if every voxel is ignored the map is all zeros and the top-k mean is 0.
+    `device_sums=True`: the Dice term of device tensors comes from `softmax_dice_sums` with mask = target != ignore_label, so the
+    loss runs wholly on the device."""
 
-    def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None):
+    def __init__(self, soft_dice_kwargs, ce_kwargs, weight_ce=1, weight_dice=1, ignore_label=None, device_sums: bool = False):
         super().__init__()
+        self.device_sums = bool(device_sums)
         ce_kwargs = dict(ce_kwargs)
         if ignore_label is not None:
             ce_kwargs["ignore_index"] = ignore_label
         self.weight_dice, self.weight_ce, self.ignore_label = weight_dice, weight_ce, ignore_label
         self.ce = TopKLoss(**ce_kwargs)
-        self.dc = SoftDiceLoss(apply_nonlin=softmax_helper_dim1, **soft_dice_kwargs)
+        self.dc = SoftDiceLoss(apply_nonlin=softmax_helper_dim1, device_sums=self.device_sums, **soft_dice_kwargs)
 
     def forward(self, net_output: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+        from . import lib as L
+        if self.device_sums and self.weight_dice != 0 and L.on_device(net_output):
+            _refuse_capture(net_output, "DC_and_topk_loss")   # the Dice sums refuse capture: say so before the top-k kernels run
         mask = None
         if self.ignore_label is not None:
             if target.dim() != net_output.dim() or target.shape[1] != 1:
@@ -381,7 +469,7 @@ def _region_sums_aten(x, target, masks, ignore_label, ignore_plane):
 def _refuse_capture(x: torch.Tensor, what: str) -> None:
     """the runtime is asked only where one is up: without a device the query itself raises"""
     if (x.is_cuda or torch.cuda.is_initialized()) and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError(f"{what}: graph capture of the region-based loss is not supported - call it outside the captured region")
+        raise RuntimeError(f"{what}: graph capture of this loss is not supported - call it outside the captured region")
 
 
 class _RegionSums(torch.autograd.Function):

@@ -1276,6 +1276,103 @@ def region_loss_bwd(lib: L.SegmLib, logits: torch.Tensor, target: torch.Tensor, 
     return dlogits
 
 
+def softmax_dice_layout_supported(logits: torch.Tensor) -> bool:
+    """whether the softmax-Dice entries take these logits as they lie in memory (a caller may pass a dense copy otherwise)"""
+    return region_loss_layout_supported(logits)
+
+
+def _softmax_dice_args(logits: torch.Tensor, labels: torch.Tensor, mask, ignore_label, what: str):
+    """the checks and the argument struct the two softmax-Dice entries share -> (args, the tensors kept alive)"""
+    if not isinstance(logits, torch.Tensor) or not isinstance(labels, torch.Tensor):
+        raise RuntimeError(f"{what}: logits and labels must be tensors")
+    if logits.dim() < 3 or logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise RuntimeError(f"{what}: logits (B, C, *spatial) fp32 / fp16 / bf16")
+    B, Cc = logits.shape[:2]
+    sp = tuple(logits.shape[2:])
+    if not 1 <= Cc <= L.SOFTMAX_DICE_MAX_CLASSES:
+        raise RuntimeError(f"{what}: 1 .. {L.SOFTMAX_DICE_MAX_CLASSES} classes, got {Cc}")
+    if logits.numel() == 0:
+        raise RuntimeError(f"{what}: empty logits {tuple(logits.shape)}")
+    if labels.device != logits.device:
+        raise RuntimeError(f"{what}: the labels lie on {labels.device}, the logits on {logits.device}")
+    V = 1
+    for s in sp:
+        V *= s
+    if V >= 1 << 31:
+        raise RuntimeError(f"{what}: {V} voxels per sample, fewer than 2^31 are supported")
+    layout = _region_layout(logits)
+    if layout is None:
+        raise RuntimeError(f"{what}: the logits need unit stride along the last axis and spatial axes in front of the last two "
+                           f"that collapse into one stride, got strides {logits.stride()} for {tuple(logits.shape)}")
+    if tuple(labels.shape) != (B,) + sp or labels.dtype not in L.REGION_LABELS:
+        raise RuntimeError(f"{what}: a label map {(B,) + sp} of int64 / int16 / uint8 / float32, got {tuple(labels.shape)} {labels.dtype}")
+    Z, Y, X, sz, sy = layout
+    st = logits.stride()
+    a = L.SoftmaxDiceArgs()
+    a.batch, a.classes, a.dtype, a.label_kind = B, Cc, L.dtype_code(logits), L.REGION_LABELS[labels.dtype]
+    a.depth, a.height, a.width = Z, Y, X
+    a.stride_b, a.stride_c, a.stride_z, a.stride_y, a.stride_x = st[0], st[1], sz, sy, 1
+    if ignore_label is not None:
+        if not -(1 << 63) <= int(ignore_label) < 1 << 63:
+            raise RuntimeError(f"{what}: ignore_label {ignore_label} is no 64-bit integer")
+        a.has_ignore, a.ignore_label = 1, int(ignore_label)
+    labels = labels.contiguous()
+    keep = [labels]
+    if mask is not None:
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (B,) + sp or mask.device != logits.device:
+            raise RuntimeError(f"{what}: the mask must be uint8 {(B,) + sp} on the logits' device")
+        mask = mask.contiguous()
+        keep.append(mask)
+        a.mask = mask.data_ptr()
+    a.logits, a.labels = logits.data_ptr(), labels.data_ptr()
+    a.stream = L.stream_handle(logits)
+    return a, keep
+
+
+def softmax_dice_fwd(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Tensor, mask: torch.Tensor = None, ignore_label: int = None,
+                     workspace: torch.Tensor = None):
+    """The sums of softmax Dice + cross entropy, float64 on the device: -> (I, P, G) of shape (B, C) and (CE, N) of shape (B).  With
+    p = softmax(logits, 1): I = sum m p_c [y = c], P = sum m p_c, G = sum m [y = c], CE = sum m (logsumexp(x) - x_y), N = sum m.
+    logits (B, C <= 16, *spatial) fp32 / fp16 / bf16, unit stride along the last axis, any batch / class / row strides; labels
+    (B, *spatial) int64 / int16 / uint8 / float32; mask optional, uint8 (B, *spatial).  m = 0 where the label equals `ignore_label`
+    or the mask is 0; any other label outside [0, C), or a float label that is no integer, gives NaN in its sample's I, P, CE."""
+    a, keep = _softmax_dice_args(logits, labels, mask, ignore_label, "softmax_dice_fwd")
+    B, Cc = logits.shape[:2]
+    nbytes = lib.dll.segm_softmax_dice_workspace_bytes(B, Cc, a.depth * a.height * a.width)
+    if nbytes == 0:
+        raise RuntimeError(f"softmax_dice_fwd: the shape {tuple(logits.shape)} is out of range")
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != logits.device or not workspace.is_contiguous():
+        raise RuntimeError("softmax_dice_fwd: the workspace must be a contiguous tensor on the logits' device")
+    sums = torch.empty(3 * B * Cc + 2 * B, dtype=torch.float64, device=logits.device)
+    a.sums = sums.data_ptr()
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    lib.check(lib.dll.segm_softmax_dice_fwd(a), "softmax_dice_fwd")
+    three = sums[:3 * B * Cc].view(3, B, Cc)
+    two = sums[3 * B * Cc:].view(2, B)
+    return three[0], three[1], three[2], two[0], two[1]
+
+
+def softmax_dice_bwd(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Tensor, g_i: torch.Tensor, g_p: torch.Tensor,
+                     g_ce: torch.Tensor, mask: torch.Tensor = None, ignore_label: int = None) -> torch.Tensor:
+    """-> dlogits_j = m (p_j (a_j - S) + g_ce (p_j - [j = y])), a_c = g_i[c] [y = c] + g_p[c], S = sum_c p_c a_c: dense, in the
+    logits' dtype and shape; exactly 0 where m = 0, NaN at a wrong label.  g_i, g_p: fp32 (B, C), g_ce: fp32 (B), on the logits'
+    device - the gradients of the loss by I, P and CE of `softmax_dice_fwd`; the other arguments as there."""
+    a, keep = _softmax_dice_args(logits, labels, mask, ignore_label, "softmax_dice_bwd")
+    B, Cc = logits.shape[:2]
+    coefs = []
+    for name, g, shape in (("g_i", g_i, (B, Cc)), ("g_p", g_p, (B, Cc)), ("g_ce", g_ce, (B,))):
+        if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != shape or g.device != logits.device:
+            raise RuntimeError(f"softmax_dice_bwd: {name} must be fp32 {shape} on the logits' device")
+        coefs.append(g.contiguous())
+    a.g_i, a.g_p, a.g_ce = (g.data_ptr() for g in coefs)
+    dlogits = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
+    a.dlogits = dlogits.data_ptr()
+    lib.check(lib.dll.segm_softmax_dice_bwd(a), "softmax_dice_bwd")
+    return dlogits
+
+
 # ---------------------------------------------------------------------------------------------------------
 # single-token decode steps
 # ---------------------------------------------------------------------------------------------------------
