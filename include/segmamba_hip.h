@@ -1479,6 +1479,74 @@ typedef struct segm_gauss_blur_args {
 int segm_gauss_blur(const segm_gauss_blur_args* args);
 
 
+/* ------------------------------------------------------------------------------------------------
+ * Intensity augmentation (additive to ABI 10; csrc/intensity.hip): noise, brightness, contrast, the two gammas and the mirror of
+ * the reference's get_train_transforms (light_training/augment/train_augment.py:40-60) as streaming passes, in place of the
+ * per-sample ATen arithmetic of SplineAugmenter (segmamba_amd/augment.py:333-363).
+ * A launch works on up to SEGM_AUG_MAX_VOLUMES planes; plane v = sample * channels + channel of a (samples, channels, depth, height,
+ * width) fp32 tensor with element strides for sample, channel, z and y, a unit stride along x and any storage offset.  Every plane
+ * carries its own op and parameters by value (all fp32), so one launch serves planes with different transforms on.  With v the
+ * input voxel and every statistic taken over the plane's voxels:
+ *   SEGM_INTENSITY_OFF       nothing: skipped in place, copied bit for bit out of place (the mirror of a plane with no op on)
+ *   SEGM_INTENSITY_NOISE     y = v + fl32(a * n), n the voxel of the plane noise[v] (dense)          augment.py:336
+ *   SEGM_INTENSITY_SCALE     y = fl32(v * a)                                                          augment.py:342
+ *   SEGM_INTENSITY_CONTRAST  u = fl32(v * a); mean, lo, hi of u; y = min(max((u - mean) * b + mean, lo), hi)   augment.py:342-348
+ *   SEGM_INTENSITY_GAMMA     t = invert ? -v : v; mean0, sd0, lo, hi of t, rng = hi - lo;
+ *                            w = max((t - lo) / (rng + 1e-7), 0) ^ a * rng + lo; mean1, sd1 of w;
+ *                            y = +-((w - mean1) / (sd1 + 1e-8) * sd0 + mean0)                         augment.py:305-315, 354
+ * sd is the population standard deviation (numpy.std, what the published transform uses).
+ * A statistics row is SEGM_INTENSITY_STATS_DOUBLES fp64: count, mean, sd, min, max, then zeros.  Rows are written by
+ * segm_intensity_stats and read by later launches from device memory: nothing is read back to the host.  Sums are taken about the
+ * plane's first value in fp64 (thread, wave shuffles, LDS, one row of partials per workgroup, a finish kernel that adds the rows in a
+ * fixed order), min and max are exact, there are no floating-point atomics: two calls are bit-equal.
+ * Refused with nothing launched: samples * channels outside [1, SEGM_AUG_MAX_VOLUMES], a side < 1, 2^31 voxels per plane or more,
+ * stride_x != 1, a negative stride or stride_y < width (SEGM_E_SHAPE); an unknown op (SEGM_E_DTYPE); a required pointer that is
+ * NULL (SEGM_E_NULL); a workspace that is NULL, misaligned (8 bytes) or smaller than segm_intensity_workspace_bytes
+ * (SEGM_E_WORKSPACE); a mirror mask on an in-place call (SEGM_E_SHAPE).  Non-finite input values are outside the contract.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_INTENSITY_OFF 0
+#define SEGM_INTENSITY_NOISE 1
+#define SEGM_INTENSITY_SCALE 2
+#define SEGM_INTENSITY_CONTRAST 3
+#define SEGM_INTENSITY_GAMMA 4
+#define SEGM_INTENSITY_STATS_DOUBLES 8
+
+typedef struct segm_intensity_args {
+    int32_t samples, channels, depth, height, width;
+    int32_t stage;                                        /* segm_intensity_stats: 0 or 1 */
+    int64_t stride_n, stride_c, stride_z, stride_y, stride_x;              /* of data */
+    int64_t out_stride_n, out_stride_c, out_stride_z, out_stride_y;        /* of out (unit stride along x) */
+    uint8_t op[SEGM_AUG_MAX_VOLUMES];
+    uint8_t invert[SEGM_AUG_MAX_VOLUMES];                 /* GAMMA on the negated plane */
+    uint8_t mirror[SEGM_AUG_MAX_VOLUMES];                 /* bit 0: flip z, bit 1: flip y, bit 2: flip x; out of place only */
+    float a[SEGM_AUG_MAX_VOLUMES];                        /* NOISE: scale; SCALE: factor; CONTRAST: pre-scale (1 = none); GAMMA: exponent */
+    float b[SEGM_AUG_MAX_VOLUMES];                        /* CONTRAST: factor */
+    const float* noise[SEGM_AUG_MAX_VOLUMES];             /* per NOISE plane: depth * height * width fp32, dense */
+    const float* data;
+    float* out;                                           /* segm_intensity_apply: NULL or == data: in place */
+    double* stats;                                        /* (planes, SEGM_INTENSITY_STATS_DOUBLES): of u (CONTRAST) / of t (GAMMA) */
+    double* stats2;                                       /* the same shape: of w (GAMMA) */
+    void* workspace;     size_t workspace_bytes;          /* segm_intensity_stats */
+    void* stream;
+} segm_intensity_args;
+
+/* 0 for a shape out of range */
+size_t segm_intensity_workspace_bytes(int32_t planes, int64_t voxels);
+
+/* stage 0: the rows `stats` of the CONTRAST planes (of u) and of the GAMMA planes (of t).  stage 1: the rows `stats2` of the GAMMA
+ * planes (of w, formed from the rows `stats` by the function the apply pass uses).  Rows of other planes are not written.  One
+ * streaming launch and one finish launch; none when no plane takes part. */
+int segm_intensity_stats(const segm_intensity_args* args);
+
+/* Every plane's op, in place (out NULL or == data; planes that are OFF are not touched) or out of place (every plane written, plane
+ * v at its mirrored position: out[z', y', x'] with z' = depth - 1 - z where bit 0 of mirror[v] is set, and so on; out must not
+ * overlap data).  CONTRAST reads its row of `stats`, GAMMA its rows of `stats` and `stats2`.  Where width, the strides in use and
+ * the base pointers are multiples of 16 bytes a thread takes a packet of 4 voxels along x (an x-mirror reverses the packet and
+ * stores it at the mirrored packet address), single voxels otherwise; both routes call the same per-voxel functions, and NOISE,
+ * SCALE and OFF give the same bits on both. */
+int segm_intensity_apply(const segm_intensity_args* args);
+
+
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);
 const char* segm_status_string(int status);

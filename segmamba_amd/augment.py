@@ -364,6 +364,136 @@ class SplineAugmenter:
         return x.contiguous(), y.contiguous()
 
 
+class FusedAugmenter(SplineAugmenter):
+    """`SplineAugmenter` with noise, brightness, contrast, the two gammas and the mirror on the kernels of csrc/intensity.hip in place
+    of the per-sample ATen arithmetic.  `draw` and the `torch.randn` calls for the noise fields are the parent's, in the parent's
+    order: for one seed the plan, the noise and the labels are `SplineAugmenter`'s.  The order of the chain is the parent's too, so
+    the fusion happens inside the three groups that blur and low resolution separate:
+
+      noise                           one apply pass
+      brightness, contrast            brightness alone: one apply pass; with contrast the factor is folded into the loads of one
+                                      statistics pass and one apply pass
+      inverted gamma, gamma, mirror   per gamma two statistics passes (of t, then of w) and one apply pass; the flips ride on the
+                                      last apply pass of the call (a plain copy pass where no gamma is on)
+
+    A pass is one launch over up to 64 planes (sample, channel), each with its own op and parameters by value; the statistics stay
+    in device memory, so a call copies nothing to the host and never waits for the device.  A pass runs in place on a tensor the call
+    owns, and out of place where the batch has a flip or where the tensor is still the caller's (which is never written).  The
+    standard deviation of the gammas is the population one (numpy.std, as in the published transform) where the ATen route takes the
+    unbiased one; the factor cancels in sd0 / sd1 and only the 1e-8 term sees it.  The label flip stays one ATen `flip` per mirrored
+    sample."""
+
+    @staticmethod
+    def _plane_groups(B, C):
+        """(samples, channels) slices with at most 64 planes each"""
+        cs = min(C, L.AUG_MAX_VOLUMES)
+        ns = max(1, L.AUG_MAX_VOLUMES // cs)
+        return [(sb, sc) for sb in SplineAugmenter._groups(B, ns) for sc in SplineAugmenter._groups(C, cs)]
+
+    def _pass(self, lib, x, ops, own, mirror=None):
+        """one fused transform of the batch: `ops[b][c]` as `ops_raw.intensity_apply` takes them, `mirror[b]` the flip mask of a
+        sample -> (x, own)"""
+        B, C = x.shape[:2]
+        flips = mirror is not None and any(mirror)
+        if not flips and not any(op is not None for row in ops for op in row):
+            return x, own
+        out_of_place = flips or not own
+        groups = self._plane_groups(B, C)
+        out = torch.empty(tuple(x.shape), dtype=x.dtype, device=x.device) if out_of_place and len(groups) > 1 else x
+        for sb, sc in groups:
+            part = x[sb, sc]
+            flat = [op for row in ops[sb] for op in row[sc]]
+            masks = [m for m in (mirror[sb] if mirror is not None else [0] * part.shape[0]) for _ in range(part.shape[1])]
+            if not out_of_place and not any(op is not None for op in flat):
+                continue
+            stats = stats2 = None
+            if any(op is not None and op[0] in ("contrast", "gamma") for op in flat):
+                stats = ops_raw.intensity_stats(lib, part, flat, 0)
+            if any(op is not None and op[0] == "gamma" for op in flat):
+                stats2 = ops_raw.intensity_stats(lib, part, flat, 1, stats)
+            if out_of_place:
+                got = ops_raw.intensity_apply(lib, part, flat, stats, stats2, masks, out_of_place=True)
+                if len(groups) == 1:
+                    out = got
+                else:
+                    out[sb, sc] = got
+            else:
+                ops_raw.intensity_apply(lib, part, flat, stats, stats2)
+        return out, True
+
+    def _noise_ops(self, x, plan):
+        """the noise fields come from the device generator, one `randn` per sample that is on, as the parent draws them"""
+        B, C = x.shape[:2]
+        ops = [[None] * C for _ in range(B)]
+        for b in np.nonzero(plan["noise_on"])[0]:
+            field = torch.randn(x.shape[1:], device=x.device, generator=self.g, dtype=x.dtype)
+            ops[b] = [("noise", float(plan["noise_scale"][b]), field[c]) for c in range(C)]
+        return ops
+
+    @staticmethod
+    def _contrast_ops(B, C, plan):
+        ops = [[None] * C for _ in range(B)]
+        for b in range(B):
+            bright = [float(m) for m in plan["bright"][b]] if plan["bright_on"][b] else [1.0] * C
+            if plan["contrast_on"][b]:
+                ops[b] = [("contrast", bright[c], float(plan["contrast"][b][c])) for c in range(C)]
+            elif plan["bright_on"][b]:
+                ops[b] = [("scale", bright[c]) for c in range(C)]
+        return ops
+
+    @staticmethod
+    def _gamma_ops(B, C, plan, key, invert):
+        return [[("gamma", float(plan[key][b][c]), invert) for c in range(C)] if plan[key + "_on"][b] else [None] * C for b in range(B)]
+
+    def _mirror_masks(self, B, plan):
+        return [sum(1 << ax for j, ax in enumerate(self.mirror_axes) if plan["mirror"][b, j]) for b in range(B)]
+
+    def _gammas_and_mirror(self, lib, x, plan, own):
+        """the last group: the passes of the gammas that are on, the flips on the last of them"""
+        B, C = x.shape[:2]
+        rounds = [ops for ops in (self._gamma_ops(B, C, plan, "gamma_inv", True), self._gamma_ops(B, C, plan, "gamma", False))
+                  if any(op is not None for row in ops for op in row)]
+        masks = self._mirror_masks(B, plan)
+        if any(masks) and not rounds:
+            rounds = [[[None] * C for _ in range(B)]]
+        for i, ops in enumerate(rounds):
+            x, own = self._pass(lib, x, ops, own, masks if i == len(rounds) - 1 else None)
+        return x, own
+
+    def __call__(self, image: torch.Tensor, label: torch.Tensor):
+        """image (B, C, D, H, W) float32, label (B, D, H, W) integer class map -> augmented copies (same shapes / dtypes)"""
+        if not L.on_device(image) or not L.on_device(label):
+            raise RuntimeError("FusedAugmenter runs on the HIP library's kernels (csrc/augment.hip, csrc/intensity.hip): image and "
+                               "label must live on the GPU; on host tensors use DeviceAugmenter (augment=True)")
+        if image.dim() != 5 or label.dim() != 4 or image.dtype != torch.float32:
+            raise RuntimeError(f"FusedAugmenter: image (B, C, D, H, W) float32 and label (B, D, H, W) are required, got "
+                               f"{tuple(image.shape)} {image.dtype} and {tuple(label.shape)}")
+        lib = L.get_lib()
+        B, C = image.shape[:2]
+        plan = self.draw(B, C, tuple(image.shape[2:]))
+        x, y = image, label
+        if self.spatial:
+            x, y = self._spatial(lib, x, y, plan)
+        own = x is not image                           # whether x may be written in place
+        own_y = y is not label
+        x, own = self._pass(lib, x, self._noise_ops(x, plan), own)
+        blurred = self._blur(lib, x, plan)
+        own, x = own or blurred is not x, blurred
+        x, own = self._pass(lib, x, self._contrast_ops(B, C, plan), own)
+        x, own = self._low_res(lib, x, plan, own)
+        x, own = self._gammas_and_mirror(lib, x, plan, own)
+        for b in range(B):
+            axes = [ax for j, ax in enumerate(self.mirror_axes) if plan["mirror"][b, j]]
+            if axes:
+                if not own_y:
+                    y, own_y = y.clone(), True
+                y[b] = y[b].flip(axes)
+        return x.contiguous(), y.contiguous()
+
+
 def select_augmenter(augment):
-    """the class behind a feeder's truthy `augment` argument: "spline" -> SplineAugmenter, anything else (True) -> DeviceAugmenter"""
+    """the class behind a feeder's truthy `augment` argument: "spline" -> SplineAugmenter, "fused" -> FusedAugmenter, anything else
+    (True) -> DeviceAugmenter"""
+    if isinstance(augment, str) and augment == "fused":
+        return FusedAugmenter
     return SplineAugmenter if isinstance(augment, str) and augment == "spline" else DeviceAugmenter

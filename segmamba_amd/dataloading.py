@@ -79,7 +79,8 @@ class PatchLoader:
     `j >= round(batch_size * (1 - oversample_foreground_percent))`, or with probability `oversample_foreground_percent` under
     `probabilistic_oversampling`; otherwise its box is uniform.  A case smaller than the patch is padded with zeros on both sides.
     All draws come from the global `np.random`, in the reference's order.  `seed` seeds the augmenter (`augment=True`: the batch of
-    `next()` goes through `augment.DeviceAugmenter`; `augment="spline"`: through `augment.SplineAugmenter`)."""
+    `next()` goes through `augment.DeviceAugmenter`; `augment="spline"`: through `augment.SplineAugmenter`; `augment="fused"`: through
+    `augment.FusedAugmenter`, the same chain with the intensity transforms and the mirror on the kernels of csrc/intensity.hip)."""
 
     def __init__(self, dataset, patch_size, batch_size: int = 2, oversample_foreground_percent: float = 0.33,
                  probabilistic_oversampling: bool = False, device=None, augment: bool = False, seed: int = 42):

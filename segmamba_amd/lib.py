@@ -308,6 +308,7 @@ EXPORTS = (
     "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
     "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
     "segm_gauss_blur",
+    "segm_intensity_workspace_bytes", "segm_intensity_stats", "segm_intensity_apply",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -549,6 +550,24 @@ class GaussBlurArgs(C.Structure):
                 ("stream", C.c_void_p)]
 
 
+# SEGM_INTENSITY_*: the op of a plane, and the doubles of a statistics row (count, mean, population sd, min, max, zeros)
+INTENSITY_OFF, INTENSITY_NOISE, INTENSITY_SCALE, INTENSITY_CONTRAST, INTENSITY_GAMMA = 0, 1, 2, 3, 4
+INTENSITY_STATS_DOUBLES = 8
+
+
+class IntensityArgs(C.Structure):
+    _fields_ = [("samples", C.c_int32), ("channels", C.c_int32), ("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("stage", C.c_int32),
+                ("stride_n", C.c_int64), ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_x", C.c_int64),
+                ("out_stride_n", C.c_int64), ("out_stride_c", C.c_int64), ("out_stride_z", C.c_int64), ("out_stride_y", C.c_int64),
+                ("op", C.c_uint8 * AUG_MAX_VOLUMES), ("invert", C.c_uint8 * AUG_MAX_VOLUMES), ("mirror", C.c_uint8 * AUG_MAX_VOLUMES),
+                ("a", C.c_float * AUG_MAX_VOLUMES), ("b", C.c_float * AUG_MAX_VOLUMES),
+                ("noise", C.c_void_p * AUG_MAX_VOLUMES),
+                ("data", C.c_void_p), ("out", C.c_void_p), ("stats", C.c_void_p), ("stats2", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 def header_abi_version() -> int:
     """SEGM_ABI_VERSION as include/segmamba_hip.h declares it (what a freshly built library must report)"""
     import re
@@ -671,6 +690,9 @@ class SegmLib:
         sig("segm_affine_labels", [C.POINTER(AffineLabelsArgs)], C.c_int)
         sig("segm_zoom_nearest", [C.POINTER(ZoomNearestArgs)], C.c_int)
         sig("segm_gauss_blur", [C.POINTER(GaussBlurArgs)], C.c_int)
+        sig("segm_intensity_workspace_bytes", [C.c_int32, C.c_int64], C.c_size_t)
+        sig("segm_intensity_stats", [C.POINTER(IntensityArgs)], C.c_int)
+        sig("segm_intensity_apply", [C.POINTER(IntensityArgs)], C.c_int)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

@@ -2439,6 +2439,128 @@ def gauss_blur(lib: L.SegmLib, x: torch.Tensor, sigma, on=None) -> torch.Tensor:
 
 
 # ---------------------------------------------------------------------------------------------------------
+# intensity augmentation (csrc/intensity.hip): noise, brightness, contrast, gamma and the mirror as streaming passes.  The op and the
+# parameters of every plane are host values and travel in the argument struct; the statistics stay on the device.
+# ---------------------------------------------------------------------------------------------------------
+def _intensity_batch(x, what: str):
+    """(N, C, D, H, W) fp32 with a unit stride along x, N * C <= 64 -> (N, C, D, H, W, stride_n, stride_c, stride_z, stride_y)"""
+    if not isinstance(x, torch.Tensor) or x.dim() != 5:
+        raise RuntimeError(f"{what}: a batch (N, C, D, H, W) is required, got {getattr(x, 'shape', type(x))}")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"{what}: float32 data are required, got {x.dtype}")
+    N, C_, D, H, W = x.shape
+    if min(x.shape) < 1 or N * C_ > L.AUG_MAX_VOLUMES:
+        raise RuntimeError(f"{what}: 1 .. {L.AUG_MAX_VOLUMES} planes (samples x channels) of at least one voxel per call, got {tuple(x.shape)}")
+    if D * H * W >= 2 ** 31:
+        raise RuntimeError(f"{what}: fewer than 2^31 voxels per plane are required, got {tuple(x.shape)}")
+    sn, sc, sz, sy, sx = x.stride()
+    if W > 1 and sx != 1:
+        raise RuntimeError(f"{what}: data need a unit stride along the last dimension")
+    if (H > 1 and sy < W) or min(sn, sc, sz) < 0:
+        raise RuntimeError(f"{what}: unsupported data strides {x.stride()}")
+    return N, C_, D, H, W, sn, sc, sz, max(sy, W)
+
+
+def _intensity_rows(t, planes: int, like: torch.Tensor, what: str) -> None:
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != (planes, L.INTENSITY_STATS_DOUBLES) \
+            or not t.is_contiguous() or t.device != like.device:
+        raise RuntimeError(f"{what}: contiguous float64 rows ({planes}, {L.INTENSITY_STATS_DOUBLES}) on {like.device} are required, got "
+                           f"{getattr(t, 'shape', type(t))} {getattr(t, 'dtype', '')}")
+
+
+def _intensity_args(x: torch.Tensor, ops, what: str):
+    """`ops`: one entry per plane n * C + c - None (off), ("noise", s, field (D, H, W)), ("scale", m), ("contrast", m, f) or
+    ("gamma", g, invert)"""
+    import math
+    N, C_, D, H, W, sn, sc, sz, sy = _intensity_batch(x, what)
+    ops = list(ops)
+    if len(ops) != N * C_:
+        raise RuntimeError(f"{what}: {N * C_} ops (one per plane) are required, got {len(ops)}")
+    a = L.IntensityArgs()
+    a.samples, a.channels, a.depth, a.height, a.width = N, C_, D, H, W
+    a.stride_n, a.stride_c, a.stride_z, a.stride_y, a.stride_x = sn, sc, sz, sy, 1
+    a.data, a.stream = x.data_ptr(), L.stream_handle(x)
+    arity = {"noise": 3, "scale": 2, "contrast": 3, "gamma": 3}
+    for v, op in enumerate(ops):
+        if op is None:
+            continue
+        if not isinstance(op, (tuple, list)) or not op or op[0] not in arity or len(op) != arity[op[0]]:
+            raise RuntimeError(f"{what}: plane {v}: None, ('noise', s, field), ('scale', m), ('contrast', m, f) or ('gamma', g, invert) "
+                               f"is required, got {op!r}")
+        kind = op[0]
+        values = [float(p) for p in (op[1:2] if kind in ("noise", "gamma") else op[1:])]
+        if not all(math.isfinite(p) for p in values):
+            raise RuntimeError(f"{what}: plane {v}: finite parameters are required, got {op[1:]!r}")
+        if kind == "noise":
+            field = op[2]
+            if not isinstance(field, torch.Tensor) or field.dtype != torch.float32 or tuple(field.shape) != (D, H, W) \
+                    or not field.is_contiguous() or field.device != x.device:
+                raise RuntimeError(f"{what}: plane {v}: a contiguous float32 noise field {(D, H, W)} on {x.device} is required, got "
+                                   f"{getattr(field, 'shape', type(field))} {getattr(field, 'dtype', '')}")
+            a.op[v], a.a[v], a.noise[v] = L.INTENSITY_NOISE, values[0], field.data_ptr()
+        elif kind == "scale":
+            a.op[v], a.a[v] = L.INTENSITY_SCALE, values[0]
+        elif kind == "contrast":
+            a.op[v], a.a[v], a.b[v] = L.INTENSITY_CONTRAST, values[0], values[1]
+        else:
+            a.op[v], a.a[v], a.invert[v] = L.INTENSITY_GAMMA, values[0], int(bool(op[2]))
+    return a, N * C_, D * H * W
+
+
+def intensity_stats(lib: L.SegmLib, x: torch.Tensor, ops, stage: int = 0, stats: torch.Tensor = None) -> torch.Tensor:
+    """x (N, C, D, H, W) fp32, N * C <= 64, `ops` as in `intensity_apply` -> float64 rows (N * C, 8) = count, mean, population sd,
+    min, max, zeros, on the device.  stage 0: of u = fl32(x m) for a contrast plane and of t = +-x for a gamma plane.  stage 1: of
+    w for a gamma plane, formed from `stats` (the rows of stage 0).  Rows of planes that take no part are not written."""
+    if stage not in (0, 1):
+        raise RuntimeError(f"intensity_stats: stage 0 or 1 is required, got {stage!r}")
+    a, planes, voxels = _intensity_args(x, ops, "intensity_stats")
+    if stage == 1:
+        _intensity_rows(stats, planes, x, "intensity_stats: stats")
+    rows = torch.empty((planes, L.INTENSITY_STATS_DOUBLES), dtype=torch.float64, device=x.device)
+    nbytes = lib.dll.segm_intensity_workspace_bytes(planes, voxels)
+    if nbytes == 0:
+        raise RuntimeError(f"intensity_stats: no workspace size for {tuple(x.shape)}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=x.device)
+    a.stage = stage
+    a.stats, a.stats2 = (rows.data_ptr(), None) if stage == 0 else (stats.data_ptr(), rows.data_ptr())
+    a.workspace, a.workspace_bytes = ws.data_ptr(), nbytes
+    lib.check(lib.dll.segm_intensity_stats(a), "intensity_stats")
+    return rows
+
+
+def intensity_apply(lib: L.SegmLib, x: torch.Tensor, ops, stats: torch.Tensor = None, stats2: torch.Tensor = None, mirror=None,
+                    out_of_place: bool = False) -> torch.Tensor:
+    """x (N, C, D, H, W) fp32, N * C <= 64; `ops`: per plane n * C + c None (off), ("noise", s, field): x + fl32(s field),
+    ("scale", m): x m, ("contrast", m, f): u = x m clipped-stretched about its mean by f, ("gamma", g, invert) - the formulas of
+    include/segmamba_hip.h.  Contrast planes read their row of `stats`, gamma planes theirs of `stats` and `stats2`
+    (`intensity_stats`, stage 0 and 1), from the device.  In place (-> x; planes that are off are not touched), or with
+    `out_of_place` into a new dense tensor, every plane at its mirrored position: `mirror` holds per plane the sum of 1 (flip z), 2 (flip
+    y) and 4 (flip x); planes that are off are copied bit for bit."""
+    a, planes, _ = _intensity_args(x, ops, "intensity_apply")
+    kinds = [int(a.op[v]) for v in range(planes)]
+    if any(k in (L.INTENSITY_CONTRAST, L.INTENSITY_GAMMA) for k in kinds):
+        _intensity_rows(stats, planes, x, "intensity_apply: stats")
+        a.stats = stats.data_ptr()
+    if L.INTENSITY_GAMMA in kinds:
+        _intensity_rows(stats2, planes, x, "intensity_apply: stats2")
+        a.stats2 = stats2.data_ptr()
+    mirror = [0] * planes if mirror is None else [int(m) for m in mirror]
+    if len(mirror) != planes or any(not 0 <= m <= 7 for m in mirror):
+        raise RuntimeError(f"intensity_apply: {planes} mirror masks in 0 .. 7 are required, got {mirror}")
+    if any(mirror) and not out_of_place:
+        raise RuntimeError("intensity_apply: a mirror needs the out-of-place form")
+    if not out_of_place:
+        lib.check(lib.dll.segm_intensity_apply(a), "intensity_apply")
+        return x
+    out = torch.empty(tuple(x.shape), dtype=torch.float32, device=x.device)
+    a.mirror[:planes] = mirror
+    a.out = out.data_ptr()
+    a.out_stride_n, a.out_stride_c, a.out_stride_z, a.out_stride_y = out.stride()[:4]
+    lib.check(lib.dll.segm_intensity_apply(a), "intensity_apply")
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -2483,5 +2605,5 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
               "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
               "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "spline_coefs", "affine_spline3", "affine_labels",
-              "zoom_nearest", "gauss_blur"):
+              "zoom_nearest", "gauss_blur", "intensity_stats", "intensity_apply"):
     globals()[_name] = _device_guard(globals()[_name])

@@ -41,7 +41,7 @@ class SyntheticBraTS:
     def __init__(self, batch: int, size: int, device, seed: int = 42, pool: int = 2, augment: bool = False):
         # augment: run the reference's training transforms on the device (segmamba_amd/augment.py) on every batch handed out
         self.augmenter = None
-        if augment:                                   # True: DeviceAugmenter; "spline": SplineAugmenter
+        if augment:                                   # True: DeviceAugmenter; "spline": SplineAugmenter; "fused": FusedAugmenter
             from .augment import select_augmenter
             self.augmenter = select_augmenter(augment)(device, seed=seed)
         g = torch.Generator(device=device).manual_seed(seed)
