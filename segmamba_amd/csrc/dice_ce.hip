@@ -7,20 +7,13 @@
 // p = softmax_c(x), label y and validity m,
 //     I = sum m p_c [y = c]     P = sum m p_c     G = sum m [y = c]   per (sample, class),
 //     CE = sum m (logsumexp(x) - x_y)     N = sum m                   per sample.
-// Written on the skeleton of region_loss.hip:
 //
-//   * sd_fwd_kernel     a workgroup owns a stretch of `chunk` voxels of one sample for ALL classes, so the label and the mask are
-//                       read once.  A thread takes packets of 16 bytes of logits along x (4 fp32, 8 fp16 / bf16) where the rows are
-//                       aligned and the instantiation knows the class count (1 .. kSdPacketMaxC), single voxels with the class
-//                       count read from the arguments otherwise; the per-voxel terms come from ONE function (sd_softmax) whose
-//                       products are rounded on their own or are explicit fused multiply-adds, so both routes compute a voxel
-//                       alike.  Every term is added in fp64 in the thread (G and N as integers), then over the wave by shuffles,
-//                       then over the four waves through LDS; the workgroup writes one row of 3 x 16 + 2 doubles.
-//   * sd_finish_kernel  one workgroup per sample adds the rows in a fixed order (wave w takes the slots w, w + 4, ..., lane l the
-//                       rows l, l + 64, ..., then a shuffle tree) and writes the (3 B C + 2 B) fp64 results.  No floating-point
-//                       atomic: two calls are bit-equal.
-//   * sd_bwd_kernel     the same packets, no reduction: the softmax again,
-//                       dlogits_j = m (p_j (a_j - S) + gCE (p_j - [j = y])),  a_c = gI_c [y = c] + gP_c,  S = sum_c p_c a_c.
+// The kernels stand on the skeleton that loss_common.h describes: sd_fwd_kernel writes rows of 3 x 16 + 2 doubles (I, P, G per class,
+// then CE and N; G and N are counted as integers in the thread) and takes the packet route where the instantiation knows the class
+// count (1 .. kLossPacketMaxN), single voxels with the class count read from the arguments otherwise; the products of its per-voxel
+// function (sd_softmax) are rounded on their own or are explicit fused multiply-adds.  loss_finish_kernel adds the rows to the
+// (3 B C + 2 B) results.  sd_bwd_kernel is
+//     dlogits_j = m (p_j (a_j - S) + gCE (p_j - [j = y])),  a_c = gI_c [y = c] + gP_c,  S = sum_c p_c a_c.
 #include <math.h>
 #include <string.h>
 
@@ -29,15 +22,11 @@
 namespace segm {
 
 constexpr int kSdMaxC = SEGM_SOFTMAX_DICE_MAX_CLASSES;
-constexpr int kSdPacketMaxC = 8;                     // the packet route knows its class count: one instantiation each for 1 .. 8
-constexpr int kSdQuantum = kBlock * 8;               // a chunk is a multiple of this: whole packets for every thread, both packet sizes
-constexpr int kSdMaxChunks = 512;                    // per sample; 128^3 voxels -> 512 chunks of 4096
 constexpr int kSdRow = 3 * kSdMaxC + 2;              // doubles of a partial row: I, P, G per class, then CE and N
-static_assert(kSdRow <= kBlock, "one thread per slot of the row");
 constexpr float kSdLog2eLo = (float)(1.4426950408889634 - (double)kLog2e);      // what kLog2e misses of log2(e)
 constexpr float kSdLn2 = 0.6931471805599453f;
 
-struct SdDev {
+struct SdDev : LossGeom {                            // n: the classes
     const void* logits;
     const void* labels;
     const uint8_t* mask;
@@ -47,10 +36,8 @@ struct SdDev {
     const float* g_i;
     const float* g_p;
     const float* g_ce;
-    int64_t sb, sc, sz, sy;
     int64_t ignore_label;
-    int32_t V, X, Y;                                 // voxels of a sample, width, height
-    int32_t B, C, kind, has_ignore, dense, chunk, nchunks;
+    int32_t kind, has_ignore;
 };
 
 // ---- the per-voxel arithmetic: one function for every route ---------------------------------------------------------------------------
@@ -124,53 +111,17 @@ __device__ __forceinline__ void sd_grad(const float x[CM], int nc, int y, const 
     }
 }
 
-// ---- addresses, labels ------------------------------------------------------------------------------------------------------------------
-// voxel v of a sample (C order over z, y, x) -> its element offset in a logits plane
-__device__ __forceinline__ int64_t sd_offset(const SdDev& P, int64_t v) {
-    if (P.dense) return v;
-    const uint32_t row = (uint32_t)v / (uint32_t)P.X, col = (uint32_t)v - row * (uint32_t)P.X;
-    const uint32_t z = row / (uint32_t)P.Y, y = row - z * (uint32_t)P.Y;
-    return (int64_t)z * P.sz + (int64_t)y * P.sy + (int64_t)col;
-}
-
-// the labels of a packet: y in [0, C), or -1 where the label names no class; ign = the label is the ignored one
-template <typename S, int N>
-__device__ __forceinline__ void sd_labels(const SdDev& P, int64_t i, int32_t y[N], bool ign[N]) {
-    S raw[N];
-    rl_load<S, N>(P.labels, i, raw);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const int64_t l = (int64_t)raw[k];
-        ign[k] = P.has_ignore && l == P.ignore_label;
-        y[k] = (l < 0 || l >= (int64_t)P.C) ? -1 : (int32_t)l;
-    }
-}
-
-template <int N>
-__device__ __forceinline__ void sd_labels_f32(const SdDev& P, int64_t i, int32_t y[N], bool ign[N]) {
-    float raw[N];
-    rl_load<float, N>(P.labels, i, raw);
-#pragma unroll
-    for (int k = 0; k < N; ++k) {
-        const float f = raw[k];
-        const bool whole = f == floorf(f) && fabsf(f) < 4.0e18f;         // NaN and inf are no integers
-        const int64_t l = whole ? (int64_t)f : (int64_t)-1;
-        ign[k] = whole && P.has_ignore && l == P.ignore_label;
-        y[k] = (!whole || l < 0 || l >= (int64_t)P.C) ? -1 : (int32_t)l;
-    }
-}
-
-// what a packet needs once for all classes: the labels, whether the voxels count (m), bit k of bad = voxel k counts and has a wrong label
+// ---- labels ----------------------------------------------------------------------------------------------------------------------------
+// what a packet needs once for all classes: the labels (y in [0, C), or -1 where the label names no class), whether the voxels count
+// (m), bit k of bad = voxel k counts and has a wrong label
 template <int N>
 __device__ __forceinline__ void sd_packet_head(const SdDev& P, int b, int64_t v, int32_t y[N], bool m[N], uint32_t& bad) {
     const int64_t i = (int64_t)b * P.V + v;
     bool ign[N];
-    switch (P.kind) {                                                     // uniform over the grid
-    case SEGM_REGION_LABELS_I64: sd_labels<int64_t, N>(P, i, y, ign); break;
-    case SEGM_REGION_LABELS_I16: sd_labels<int16_t, N>(P, i, y, ign); break;
-    case SEGM_REGION_LABELS_U8: sd_labels<uint8_t, N>(P, i, y, ign); break;
-    default: sd_labels_f32<N>(P, i, y, ign); break;
-    }
+    loss_labels<N>(P.labels, P.kind, i, [&](int k, int64_t l, bool whole) {
+        ign[k] = whole && P.has_ignore && l == P.ignore_label;
+        y[k] = (!whole || l < 0 || l >= (int64_t)P.n) ? -1 : (int32_t)l;
+    });
 #pragma unroll
     for (int k = 0; k < N; ++k) m[k] = !ign[k];
     if (P.mask) {
@@ -190,7 +141,7 @@ template <typename T, bool VEC, int CT>
 __global__ void __launch_bounds__(kBlock) sd_fwd_kernel(SdDev P) {
     constexpr int N = VEC ? Vec<T>::N : 1;
     constexpr int CM = CT ? CT : kSdMaxC;
-    const int nc = CT ? CT : P.C;
+    const int nc = CT ? CT : P.n;
     __shared__ double s_part[kWavesPerBlock][kSdRow];
     const int b = blockIdx.y;
     const int64_t lo = (int64_t)blockIdx.x * P.chunk;
@@ -208,11 +159,11 @@ __global__ void __launch_bounds__(kBlock) sd_fwd_kernel(SdDev P) {
         int32_t y[N];
         bool m[N];
         sd_packet_head<N>(P, b, v, y, m, bad);
-        const int64_t off = sd_offset(P, v);
+        const int64_t off = loss_offset(P, v);
         Pack<T, VEC> x[CM];
 #pragma unroll
         for (int c = 0; c < CM; ++c)
-            if (c < nc) x[c].load(xb + (int64_t)c * P.sc + off);
+            if (c < nc) x[c].load(xb + (int64_t)c * P.sn + off);
 #pragma unroll
         for (int k = 0; k < N; ++k) {
             if (m[k]) {
@@ -248,31 +199,7 @@ __global__ void __launch_bounds__(kBlock) sd_fwd_kernel(SdDev P) {
     }
     const double sCE = rl_wave_sum(aCE + poison), sN = rl_wave_sum((double)count);
     if (lane == 0) { s_part[wave][3 * kSdMaxC] = sCE; s_part[wave][3 * kSdMaxC + 1] = sN; }
-    __syncthreads();
-    if ((int)threadIdx.x < kSdRow) {
-        double s = s_part[0][threadIdx.x];
-        for (int w = 1; w < kWavesPerBlock; ++w) s += s_part[w][threadIdx.x];
-        P.part[((int64_t)b * P.nchunks + blockIdx.x) * kSdRow + threadIdx.x] = s;
-    }
-}
-
-// one workgroup per sample: wave w takes the slots w, w + 4, ...; lane l the rows l, l + 64, ...; then a shuffle tree
-__global__ void __launch_bounds__(kBlock) sd_finish_kernel(SdDev P) {
-    const int b = blockIdx.x;
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const double* rows = P.part + (int64_t)b * P.nchunks * kSdRow;
-    const int64_t bc = (int64_t)P.B * P.C;
-    for (int slot = wave; slot < kSdRow; slot += kWavesPerBlock) {
-        const int q = slot / kSdMaxC, c = slot - q * kSdMaxC;
-        if (q < 3 && c >= P.C) continue;             // uniform over the wave
-        double acc = 0.0;
-        for (int r = lane; r < P.nchunks; r += kWave) acc += rows[(int64_t)r * kSdRow + slot];
-        acc = rl_wave_sum(acc);
-        if (lane == 0) {
-            if (q < 3) P.sums[q * bc + (int64_t)b * P.C + c] = acc;
-            else P.sums[3 * bc + (int64_t)c * P.B + b] = acc;      // c = 0: CE, c = 1: N
-        }
-    }
+    loss_block_row<kSdRow>(s_part, P.part, b, P.nchunks, blockIdx.x);
 }
 
 // ---- backward ---------------------------------------------------------------------------------------------------------------------------
@@ -280,25 +207,25 @@ template <typename T, bool VEC, int CT>
 __global__ void __launch_bounds__(kBlock) sd_bwd_kernel(SdDev P) {
     constexpr int N = VEC ? Vec<T>::N : 1;
     constexpr int CM = CT ? CT : kSdMaxC;
-    const int nc = CT ? CT : P.C;
+    const int nc = CT ? CT : P.n;
     const int b = blockIdx.y;
     const int64_t v = ((int64_t)blockIdx.x * kBlock + threadIdx.x) * N;
     if (v >= P.V) return;
     const T* xb = reinterpret_cast<const T*>(P.logits) + (int64_t)b * P.sb;
-    T* db = reinterpret_cast<T*>(P.dlogits) + (int64_t)b * P.C * P.V + v;
+    T* db = reinterpret_cast<T*>(P.dlogits) + (int64_t)b * P.n * P.V + v;
     int32_t y[N];
     bool m[N];
     uint32_t bad = 0;
     sd_packet_head<N>(P, b, v, y, m, bad);
-    const int64_t off = sd_offset(P, v);
+    const int64_t off = loss_offset(P, v);
     Pack<T, VEC> x[CM];
     float gi[CM], gp[CM];
 #pragma unroll
     for (int c = 0; c < CM; ++c) {
         if (c < nc) {
-            x[c].load(xb + (int64_t)c * P.sc + off);
-            gi[c] = P.g_i[b * P.C + c];
-            gp[c] = P.g_p[b * P.C + c];
+            x[c].load(xb + (int64_t)c * P.sn + off);
+            gi[c] = P.g_i[b * P.n + c];
+            gp[c] = P.g_p[b * P.n + c];
         } else {
             gi[c] = gp[c] = 0.f;
         }
@@ -320,50 +247,19 @@ __global__ void __launch_bounds__(kBlock) sd_bwd_kernel(SdDev P) {
 }
 
 // ---- host -------------------------------------------------------------------------------------------------------------------------------
-static int32_t sd_chunk(int64_t voxels) {
-    const int64_t per = (voxels + kSdMaxChunks - 1) / kSdMaxChunks;
-    const int64_t chunk = ((per + kSdQuantum - 1) / kSdQuantum) * kSdQuantum;
-    return (int32_t)(chunk < kSdQuantum ? kSdQuantum : chunk);
-}
-
-static size_t sd_label_esize(int kind) {
-    switch (kind) {
-    case SEGM_REGION_LABELS_I64: return 8;
-    case SEGM_REGION_LABELS_I16: return 2;
-    case SEGM_REGION_LABELS_U8: return 1;
-    default: return 4;
-    }
-}
-
 // the checks the two entries share; 0 or a SEGM_E_* status.  `vec` tells whether the packet route may be taken.
 static int sd_setup(const segm_softmax_dice_args* a, SdDev& P, bool& vec) {
     if (!a) return SEGM_E_NULL;
-    if (a->batch <= 0 || a->classes < 1 || a->classes > kSdMaxC || a->depth <= 0 || a->height <= 0 || a->width <= 0) return SEGM_E_SHAPE;
-    if (a->batch > 65535) return SEGM_E_SHAPE;                            // the grid's y
-    const int64_t voxels = (int64_t)a->depth * a->height * a->width;
-    if (voxels >= ((int64_t)1 << 31)) return SEGM_E_SHAPE;
-    if (a->stride_x != 1 || a->stride_b < 0 || a->stride_c < 0 || a->stride_z < 0 || a->stride_y < 0) return SEGM_E_SHAPE;
-    if (a->dtype != SEGM_F32 && a->dtype != SEGM_F16 && a->dtype != SEGM_BF16) return SEGM_E_DTYPE;
-    if (a->label_kind < SEGM_REGION_LABELS_I64 || a->label_kind > SEGM_REGION_LABELS_F32) return SEGM_E_DTYPE;
-    if (!a->logits || !a->labels) return SEGM_E_NULL;
-    const size_t esize = a->dtype == SEGM_F32 ? 4 : 2;
-    if ((uintptr_t)a->logits % esize || (uintptr_t)a->labels % sd_label_esize(a->label_kind)) return SEGM_E_SHAPE;
+    const int own = a->label_kind < SEGM_REGION_LABELS_I64 || a->label_kind > SEGM_REGION_LABELS_F32 ? SEGM_E_DTYPE : SEGM_OK;
     memset(&P, 0, sizeof(P));
+    const int rc = loss_setup(a, a->classes, kSdMaxC, a->stride_c, a->labels, a->label_kind, own, P);
+    if (rc != SEGM_OK) return rc;
     P.logits = a->logits; P.labels = a->labels; P.mask = a->mask;
-    P.sb = a->stride_b; P.sc = a->stride_c; P.sz = a->stride_z; P.sy = a->stride_y;
     P.ignore_label = a->ignore_label;
     P.has_ignore = a->has_ignore ? 1 : 0;
-    P.V = (int32_t)voxels; P.X = a->width; P.Y = a->height;
-    P.B = a->batch; P.C = a->classes; P.kind = a->label_kind;
-    P.dense = (a->height == 1 || a->stride_y == a->width) && (a->depth == 1 || a->stride_z == (int64_t)a->width * a->height);
-    P.chunk = sd_chunk(voxels);
-    P.nchunks = (int32_t)((voxels + P.chunk - 1) / P.chunk);
-    // packets: every row starts at a multiple of 16 bytes in the logits and at a multiple of the packet in the dense labels and mask
-    // (the strides of axes of size 1 are never used)
-    const int64_t n = (int64_t)(16 / esize);
-    vec = a->classes <= kSdPacketMaxC && a->width % n == 0 && (a->batch == 1 || a->stride_b % n == 0) &&
-          (a->classes == 1 || a->stride_c % n == 0) && (a->depth == 1 || a->stride_z % n == 0) &&
-          (a->height == 1 || a->stride_y % n == 0) && (uintptr_t)a->logits % 16 == 0 && (uintptr_t)a->labels % 16 == 0 &&
+    P.kind = a->label_kind;
+    // the dense labels and mask: whole packets
+    vec = a->classes <= kLossPacketMaxN && loss_rows_aligned(a, a->classes, a->stride_c) && (uintptr_t)a->labels % 16 == 0 &&
           (uintptr_t)a->mask % 16 == 0;
     return SEGM_OK;
 }
@@ -373,18 +269,8 @@ static int sd_setup(const segm_softmax_dice_args* a, SdDev& P, bool& vec) {
 using namespace segm;
 
 extern "C" size_t segm_softmax_dice_workspace_bytes(int32_t batch, int32_t classes, int64_t voxels) {
-    if (batch <= 0 || batch > 65535 || classes < 1 || classes > kSdMaxC || voxels < 1 || voxels >= ((int64_t)1 << 31)) return 0;
-    const int32_t chunk = sd_chunk(voxels);
-    const int64_t nchunks = (voxels + chunk - 1) / chunk;
-    return (size_t)batch * (size_t)nchunks * kSdRow * sizeof(double);
+    return loss_workspace_bytes(batch, classes, kSdMaxC, voxels, kSdRow);
 }
-
-#define SEGM_SD_CASE(K, T, CT) case CT: hipLaunchKernelGGL((K<T, true, CT>), grid, dim3(kBlock), 0, st, P); break
-#define SEGM_SD_LAUNCH(K, T) \
-    do { if (vec) switch (P.C) { SEGM_SD_CASE(K, T, 1); SEGM_SD_CASE(K, T, 2); SEGM_SD_CASE(K, T, 3); SEGM_SD_CASE(K, T, 4); \
-                                 SEGM_SD_CASE(K, T, 5); SEGM_SD_CASE(K, T, 6); SEGM_SD_CASE(K, T, 7); SEGM_SD_CASE(K, T, 8); } \
-         else hipLaunchKernelGGL((K<T, false, 0>), grid, dim3(kBlock), 0, st, P); } while (0)
-static_assert(kSdPacketMaxC == 8, "one case per packet instantiation");
 
 extern "C" int segm_softmax_dice_fwd(const segm_softmax_dice_args* a) {
     SdDev P;
@@ -399,10 +285,8 @@ extern "C" int segm_softmax_dice_fwd(const segm_softmax_dice_args* a) {
     P.sums = a->sums;
     const dim3 grid((unsigned)P.nchunks, (unsigned)P.B);
     hipStream_t st = (hipStream_t)a->stream;
-    if (a->dtype == SEGM_F32) SEGM_SD_LAUNCH(sd_fwd_kernel, float);
-    else if (a->dtype == SEGM_F16) SEGM_SD_LAUNCH(sd_fwd_kernel, f16_t);
-    else SEGM_SD_LAUNCH(sd_fwd_kernel, bf16_t);
-    hipLaunchKernelGGL(sd_finish_kernel, dim3((unsigned)P.B), dim3(kBlock), 0, st, P);
+    SEGM_LOSS_LAUNCH(sd_fwd_kernel, a->dtype);
+    hipLaunchKernelGGL((loss_finish_kernel<kSdRow, 3, kSdMaxC>), dim3((unsigned)P.B), dim3(kBlock), 0, st, P.part, P.sums, P.nchunks, P.n, P.B);
     return (int)hipGetLastError();
 }
 
@@ -417,14 +301,8 @@ extern "C" int segm_softmax_dice_bwd(const segm_softmax_dice_args* a) {
         (uintptr_t)a->g_ce % sizeof(float)) return SEGM_E_SHAPE;
     vec = vec && (uintptr_t)a->dlogits % 16 == 0;
     P.dlogits = a->dlogits; P.g_i = a->g_i; P.g_p = a->g_p; P.g_ce = a->g_ce;
-    const int64_t n = vec ? (int64_t)(16 / esize) : 1;
-    const int64_t packets = ((int64_t)P.V + n - 1) / n;
-    const dim3 grid((unsigned)((packets + kBlock - 1) / kBlock), (unsigned)P.B);
+    const dim3 grid = loss_bwd_grid(P, vec, a->dtype);
     hipStream_t st = (hipStream_t)a->stream;
-    if (a->dtype == SEGM_F32) SEGM_SD_LAUNCH(sd_bwd_kernel, float);
-    else if (a->dtype == SEGM_F16) SEGM_SD_LAUNCH(sd_bwd_kernel, f16_t);
-    else SEGM_SD_LAUNCH(sd_bwd_kernel, bf16_t);
+    SEGM_LOSS_LAUNCH(sd_bwd_kernel, a->dtype);
     return (int)hipGetLastError();
 }
-#undef SEGM_SD_LAUNCH
-#undef SEGM_SD_CASE

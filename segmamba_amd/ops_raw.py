@@ -1144,8 +1144,8 @@ def cross_entropy_map_bwd(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Te
     return dlogits
 
 
-def _region_layout(logits: torch.Tensor):
-    """the spatial axes of (B, R, *spatial) logits as (z, y, x) - x the last axis, y the one before, z whatever lies in front, which
+def _loss_layout(logits: torch.Tensor):
+    """the spatial axes of (B, n, *spatial) logits as (z, y, x) - x the last axis, y the one before, z whatever lies in front, which
     one stride must serve -> (Z, Y, X, stride_z, stride_y), or None where the strides do not allow it"""
     sp, st = tuple(logits.shape[2:]), logits.stride()
     X = sp[-1]
@@ -1168,38 +1168,82 @@ def _region_layout(logits: torch.Tensor):
 
 def region_loss_layout_supported(logits: torch.Tensor) -> bool:
     """whether the region-loss entries take these logits as they lie in memory (a caller may pass a dense copy otherwise)"""
-    return logits.dim() >= 3 and logits.numel() > 0 and _region_layout(logits) is not None
+    return logits.dim() >= 3 and logits.numel() > 0 and _loss_layout(logits) is not None
+
+
+def softmax_dice_layout_supported(logits: torch.Tensor) -> bool:
+    """whether the softmax-Dice entries take these logits as they lie in memory (a caller may pass a dense copy otherwise)"""
+    return region_loss_layout_supported(logits)
+
+
+def _loss_logits_args(a, logits: torch.Tensor, other: torch.Tensor, other_name: str, planes: str, limit: int, what: str) -> None:
+    """the checks of the logits (B, n, *spatial) that the region-loss and the softmax-Dice entries share, and the fields of their
+    argument structs that describe them.  `planes` is "regions" or "classes": the struct's field for n, and the stride field by its
+    first letter; `other` is the target / the labels, which must be a tensor on the logits' device."""
+    if not isinstance(logits, torch.Tensor) or not isinstance(other, torch.Tensor):
+        raise RuntimeError(f"{what}: logits and {other_name} must be tensors")
+    if logits.dim() < 3 or logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
+        raise RuntimeError(f"{what}: logits (B, {planes[0].upper()}, *spatial) fp32 / fp16 / bf16")
+    B, n = logits.shape[:2]
+    if not 1 <= n <= limit:
+        raise RuntimeError(f"{what}: 1 .. {limit} {planes}, got {n}")
+    if logits.numel() == 0:
+        raise RuntimeError(f"{what}: empty logits {tuple(logits.shape)}")
+    if other.device != logits.device:
+        raise RuntimeError(f"{what}: {other_name} on {other.device}, the logits on {logits.device}")
+    V = 1
+    for s in logits.shape[2:]:
+        V *= s
+    if V >= 1 << 31:
+        raise RuntimeError(f"{what}: {V} voxels per sample, fewer than 2^31 are supported")
+    layout = _loss_layout(logits)
+    if layout is None:
+        raise RuntimeError(f"{what}: the logits need unit stride along the last axis and spatial axes in front of the last two "
+                           f"that collapse into one stride, got strides {logits.stride()} for {tuple(logits.shape)}")
+    st = logits.stride()
+    a.batch, a.dtype = B, L.dtype_code(logits)
+    setattr(a, planes, n)
+    setattr(a, "stride_" + planes[0], st[1])
+    a.depth, a.height, a.width, a.stride_z, a.stride_y = layout
+    a.stride_b, a.stride_x = st[0], 1
+    a.logits, a.stream = logits.data_ptr(), L.stream_handle(logits)
+
+
+def _loss_ignore_label(a, ignore_label, what: str) -> None:
+    if ignore_label is not None:
+        if not -(1 << 63) <= int(ignore_label) < 1 << 63:
+            raise RuntimeError(f"{what}: ignore_label {ignore_label} is no 64-bit integer")
+        a.has_ignore, a.ignore_label = 1, int(ignore_label)
+
+
+def _loss_workspace(a, nbytes: int, workspace, logits: torch.Tensor, what: str) -> torch.Tensor:
+    """the forward's workspace of `nbytes` (what the entry's *_workspace_bytes answered), allocated unless the caller brings one"""
+    if nbytes == 0:
+        raise RuntimeError(f"{what}: the shape {tuple(logits.shape)} is out of range")
+    if workspace is None:
+        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.device != logits.device or not workspace.is_contiguous():
+        raise RuntimeError(f"{what}: the workspace must be a contiguous tensor on the logits' device")
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    return workspace
+
+
+def _loss_coefs(coefs, logits: torch.Tensor, what: str):
+    """the backward's coefficients, (name, tensor, shape) each: fp32 of that shape on the logits' device -> them, contiguous"""
+    out = []
+    for name, g, shape in coefs:
+        if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != shape or g.device != logits.device:
+            raise RuntimeError(f"{what}: {name} must be fp32 {shape} on the logits' device")
+        out.append(g.contiguous())
+    return out
 
 
 def _region_args(logits: torch.Tensor, target: torch.Tensor, masks, ignore_label, ignore_plane: bool, what: str):
     """the checks and the argument struct the two region-loss entries share -> (args, target kept alive)"""
-    if not isinstance(logits, torch.Tensor) or not isinstance(target, torch.Tensor):
-        raise RuntimeError(f"{what}: logits and target must be tensors")
-    if logits.dim() < 3 or logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise RuntimeError(f"{what}: logits (B, R, *spatial) fp32 / fp16 / bf16")
+    a = L.RegionLossArgs()
+    _loss_logits_args(a, logits, target, "target", "regions", L.REGION_MAX_REGIONS, what)
     B, R = logits.shape[:2]
     sp = tuple(logits.shape[2:])
-    if not 1 <= R <= L.REGION_MAX_REGIONS:
-        raise RuntimeError(f"{what}: 1 .. {L.REGION_MAX_REGIONS} regions, got {R}")
-    if logits.numel() == 0:
-        raise RuntimeError(f"{what}: empty logits {tuple(logits.shape)}")
-    if target.device != logits.device:
-        raise RuntimeError(f"{what}: the target lies on {target.device}, the logits on {logits.device}")
-    V = 1
-    for s in sp:
-        V *= s
-    if V >= 1 << 31:
-        raise RuntimeError(f"{what}: {V} voxels per sample, fewer than 2^31 are supported")
-    layout = _region_layout(logits)
-    if layout is None:
-        raise RuntimeError(f"{what}: the logits need unit stride along the last axis and spatial axes in front of the last two "
-                           f"that collapse into one stride, got strides {logits.stride()} for {tuple(logits.shape)}")
-    Z, Y, X, sz, sy = layout
-    st = logits.stride()
-    a = L.RegionLossArgs()
-    a.batch, a.regions, a.dtype = B, R, L.dtype_code(logits)
-    a.depth, a.height, a.width = Z, Y, X
-    a.stride_b, a.stride_r, a.stride_z, a.stride_y, a.stride_x = st[0], st[1], sz, sy, 1
     if masks is not None:
         if ignore_plane:
             raise RuntimeError(f"{what}: an ignore plane belongs to a plane target, not to a label map")
@@ -1212,10 +1256,7 @@ def _region_args(logits: torch.Tensor, target: torch.Tensor, masks, ignore_label
         a.target_kind = L.REGION_LABELS[target.dtype]
         for r, m in enumerate(masks):
             a.masks[r] = m
-        if ignore_label is not None:
-            if not -(1 << 63) <= int(ignore_label) < 1 << 63:
-                raise RuntimeError(f"{what}: ignore_label {ignore_label} is no 64-bit integer")
-            a.has_ignore, a.ignore_label = 1, int(ignore_label)
+        _loss_ignore_label(a, ignore_label, what)
     else:
         if ignore_label is not None:
             raise RuntimeError(f"{what}: ignore_label belongs to a label map (pass masks), a plane target takes ignore_plane")
@@ -1227,8 +1268,7 @@ def _region_args(logits: torch.Tensor, target: torch.Tensor, masks, ignore_label
                                f"{target.dtype}")
         a.target_kind, a.ignore_plane = L.REGION_PLANES[target.dtype], int(bool(ignore_plane))
     target = target.contiguous()
-    a.logits, a.target = logits.data_ptr(), target.data_ptr()
-    a.stream = L.stream_handle(logits)
+    a.target = target.data_ptr()
     return a, target
 
 
@@ -1243,15 +1283,9 @@ def region_loss_fwd(lib: L.SegmLib, logits: torch.Tensor, target: torch.Tensor, 
     a, target = _region_args(logits, target, masks, ignore_label, ignore_plane, "region_loss_fwd")
     B, R = logits.shape[:2]
     nbytes = lib.dll.segm_region_loss_workspace_bytes(B, R, a.depth * a.height * a.width)
-    if nbytes == 0:
-        raise RuntimeError(f"region_loss_fwd: the shape {tuple(logits.shape)} is out of range")
-    if workspace is None:
-        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
-    elif not isinstance(workspace, torch.Tensor) or workspace.device != logits.device or not workspace.is_contiguous():
-        raise RuntimeError("region_loss_fwd: the workspace must be a contiguous tensor on the logits' device")
+    workspace = _loss_workspace(a, nbytes, workspace, logits, "region_loss_fwd")
     sums = torch.empty(4 * B * R + B, dtype=torch.float64, device=logits.device)
     a.sums = sums.data_ptr()
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     lib.check(lib.dll.segm_region_loss_fwd(a), "region_loss_fwd")
     four = sums[:4 * B * R].view(4, B, R)
     return four[0], four[1], four[2], four[3], sums[4 * B * R:]
@@ -1263,12 +1297,8 @@ def region_loss_bwd(lib: L.SegmLib, logits: torch.Tensor, target: torch.Tensor, 
     wrong label.  g_i, g_p, g_e: fp32 (B, R) on the logits' device, the gradients of the loss by I, P and E of `region_loss_fwd`;
     the other arguments as there."""
     a, target = _region_args(logits, target, masks, ignore_label, ignore_plane, "region_loss_bwd")
-    B, R = logits.shape[:2]
-    coefs = []
-    for name, g in (("g_i", g_i), ("g_p", g_p), ("g_e", g_e)):
-        if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != (B, R) or g.device != logits.device:
-            raise RuntimeError(f"region_loss_bwd: {name} must be fp32 {(B, R)} on the logits' device")
-        coefs.append(g.contiguous())
+    BR = tuple(logits.shape[:2])
+    coefs = _loss_coefs((("g_i", g_i, BR), ("g_p", g_p, BR), ("g_e", g_e, BR)), logits, "region_loss_bwd")
     a.g_i, a.g_p, a.g_e = (g.data_ptr() for g in coefs)
     dlogits = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
     a.dlogits = dlogits.data_ptr()
@@ -1276,56 +1306,24 @@ def region_loss_bwd(lib: L.SegmLib, logits: torch.Tensor, target: torch.Tensor, 
     return dlogits
 
 
-def softmax_dice_layout_supported(logits: torch.Tensor) -> bool:
-    """whether the softmax-Dice entries take these logits as they lie in memory (a caller may pass a dense copy otherwise)"""
-    return region_loss_layout_supported(logits)
-
-
 def _softmax_dice_args(logits: torch.Tensor, labels: torch.Tensor, mask, ignore_label, what: str):
     """the checks and the argument struct the two softmax-Dice entries share -> (args, the tensors kept alive)"""
-    if not isinstance(logits, torch.Tensor) or not isinstance(labels, torch.Tensor):
-        raise RuntimeError(f"{what}: logits and labels must be tensors")
-    if logits.dim() < 3 or logits.dtype not in (torch.float32, torch.float16, torch.bfloat16):
-        raise RuntimeError(f"{what}: logits (B, C, *spatial) fp32 / fp16 / bf16")
-    B, Cc = logits.shape[:2]
-    sp = tuple(logits.shape[2:])
-    if not 1 <= Cc <= L.SOFTMAX_DICE_MAX_CLASSES:
-        raise RuntimeError(f"{what}: 1 .. {L.SOFTMAX_DICE_MAX_CLASSES} classes, got {Cc}")
-    if logits.numel() == 0:
-        raise RuntimeError(f"{what}: empty logits {tuple(logits.shape)}")
-    if labels.device != logits.device:
-        raise RuntimeError(f"{what}: the labels lie on {labels.device}, the logits on {logits.device}")
-    V = 1
-    for s in sp:
-        V *= s
-    if V >= 1 << 31:
-        raise RuntimeError(f"{what}: {V} voxels per sample, fewer than 2^31 are supported")
-    layout = _region_layout(logits)
-    if layout is None:
-        raise RuntimeError(f"{what}: the logits need unit stride along the last axis and spatial axes in front of the last two "
-                           f"that collapse into one stride, got strides {logits.stride()} for {tuple(logits.shape)}")
-    if tuple(labels.shape) != (B,) + sp or labels.dtype not in L.REGION_LABELS:
-        raise RuntimeError(f"{what}: a label map {(B,) + sp} of int64 / int16 / uint8 / float32, got {tuple(labels.shape)} {labels.dtype}")
-    Z, Y, X, sz, sy = layout
-    st = logits.stride()
     a = L.SoftmaxDiceArgs()
-    a.batch, a.classes, a.dtype, a.label_kind = B, Cc, L.dtype_code(logits), L.REGION_LABELS[labels.dtype]
-    a.depth, a.height, a.width = Z, Y, X
-    a.stride_b, a.stride_c, a.stride_z, a.stride_y, a.stride_x = st[0], st[1], sz, sy, 1
-    if ignore_label is not None:
-        if not -(1 << 63) <= int(ignore_label) < 1 << 63:
-            raise RuntimeError(f"{what}: ignore_label {ignore_label} is no 64-bit integer")
-        a.has_ignore, a.ignore_label = 1, int(ignore_label)
+    _loss_logits_args(a, logits, labels, "labels", "classes", L.SOFTMAX_DICE_MAX_CLASSES, what)
+    shape = (logits.shape[0],) + tuple(logits.shape[2:])
+    if tuple(labels.shape) != shape or labels.dtype not in L.REGION_LABELS:
+        raise RuntimeError(f"{what}: a label map {shape} of int64 / int16 / uint8 / float32, got {tuple(labels.shape)} {labels.dtype}")
+    a.label_kind = L.REGION_LABELS[labels.dtype]
+    _loss_ignore_label(a, ignore_label, what)
     labels = labels.contiguous()
     keep = [labels]
     if mask is not None:
-        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != (B,) + sp or mask.device != logits.device:
-            raise RuntimeError(f"{what}: the mask must be uint8 {(B,) + sp} on the logits' device")
+        if not isinstance(mask, torch.Tensor) or mask.dtype != torch.uint8 or tuple(mask.shape) != shape or mask.device != logits.device:
+            raise RuntimeError(f"{what}: the mask must be uint8 {shape} on the logits' device")
         mask = mask.contiguous()
         keep.append(mask)
         a.mask = mask.data_ptr()
-    a.logits, a.labels = logits.data_ptr(), labels.data_ptr()
-    a.stream = L.stream_handle(logits)
+    a.labels = labels.data_ptr()
     return a, keep
 
 
@@ -1339,15 +1337,9 @@ def softmax_dice_fwd(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Tensor,
     a, keep = _softmax_dice_args(logits, labels, mask, ignore_label, "softmax_dice_fwd")
     B, Cc = logits.shape[:2]
     nbytes = lib.dll.segm_softmax_dice_workspace_bytes(B, Cc, a.depth * a.height * a.width)
-    if nbytes == 0:
-        raise RuntimeError(f"softmax_dice_fwd: the shape {tuple(logits.shape)} is out of range")
-    if workspace is None:
-        workspace = torch.empty(nbytes // 8, dtype=torch.float64, device=logits.device)
-    elif not isinstance(workspace, torch.Tensor) or workspace.device != logits.device or not workspace.is_contiguous():
-        raise RuntimeError("softmax_dice_fwd: the workspace must be a contiguous tensor on the logits' device")
+    workspace = _loss_workspace(a, nbytes, workspace, logits, "softmax_dice_fwd")
     sums = torch.empty(3 * B * Cc + 2 * B, dtype=torch.float64, device=logits.device)
     a.sums = sums.data_ptr()
-    a.workspace, a.workspace_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     lib.check(lib.dll.segm_softmax_dice_fwd(a), "softmax_dice_fwd")
     three = sums[:3 * B * Cc].view(3, B, Cc)
     two = sums[3 * B * Cc:].view(2, B)
@@ -1360,12 +1352,8 @@ def softmax_dice_bwd(lib: L.SegmLib, logits: torch.Tensor, labels: torch.Tensor,
     logits' dtype and shape; exactly 0 where m = 0, NaN at a wrong label.  g_i, g_p: fp32 (B, C), g_ce: fp32 (B), on the logits'
     device - the gradients of the loss by I, P and CE of `softmax_dice_fwd`; the other arguments as there."""
     a, keep = _softmax_dice_args(logits, labels, mask, ignore_label, "softmax_dice_bwd")
-    B, Cc = logits.shape[:2]
-    coefs = []
-    for name, g, shape in (("g_i", g_i, (B, Cc)), ("g_p", g_p, (B, Cc)), ("g_ce", g_ce, (B,))):
-        if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != shape or g.device != logits.device:
-            raise RuntimeError(f"softmax_dice_bwd: {name} must be fp32 {shape} on the logits' device")
-        coefs.append(g.contiguous())
+    BC = tuple(logits.shape[:2])
+    coefs = _loss_coefs((("g_i", g_i, BC), ("g_p", g_p, BC), ("g_ce", g_ce, BC[:1])), logits, "softmax_dice_bwd")
     a.g_i, a.g_p, a.g_ce = (g.data_ptr() for g in coefs)
     dlogits = torch.empty(logits.shape, dtype=logits.dtype, device=logits.device)
     a.dlogits = dlogits.data_ptr()
