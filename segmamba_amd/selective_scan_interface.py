@@ -8,11 +8,11 @@ Same names, argument order, layouts ((batch, dim, seqlen) tensors, B/C as (batch
 seqlen)) and error behaviour.  What changes underneath:
 
   * the native ops are `segm_*` entry points of libsegmamba_hip.so (no fallback if it is missing);
-  * the inner pipeline exists once (`MambaInnerCore`) and is layout- and time-order-generic: the reference
-    entry points call it with channel-first views, `Mamba.forward` calls it on the channel-last (B, L, 2D)
-    tensor the in-projection GEMM naturally produces, with the reversed / slice-interleaved directions as
-    an index map inside the kernels instead of `flip` / `stack` / `permute` copies
-    (reference mamba_simple.py:231,245-247,261);
+  * the inner pipeline's per-direction steps exist once, as functions over a `_direction` record, layout- and time-order-generic,
+    and two autograd nodes orchestrate them.  `MambaInnerCore` runs one direction: the reference entry points call it with
+    channel-first views, `Mamba` on the channel-last (B, L, 2D) tensor the in-projection GEMM naturally produces, with the
+    reversed / slice-interleaved directions as an index map inside the kernels instead of `flip` / `stack` / `permute` copies
+    (reference mamba_simple.py:231,245-247,261).  `MambaInnerCore3` runs a v3 layer's three directions around `_multi` launches;
   * B and C are never transposed into separate contiguous tensors (reference :193,205): the scan reads
     them as strided views of `x_dbl`, and dB / dC are accumulated straight into the matching columns of
     the fp32 `dx_dbl` buffer (reference :257-268 does two more transposing copies).
@@ -20,6 +20,7 @@ seqlen)) and error behaviour.  What changes underneath:
 from __future__ import annotations
 
 import os
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -163,6 +164,137 @@ _FUSED_DTPROJ = os.environ.get("SEGM_SCAN_FUSED_DTPROJ", "0") == "1"     # dt_pr
 # ---------------------------------------------------------------------------------------------------------
 # fused inner pipeline: conv1d+SiLU -> x_proj -> dt_proj -> selective scan (gated by silu(z))
 # ---------------------------------------------------------------------------------------------------------
+def _direction(conv_w, conv_b, xw, dtw, A, D, dbias, Bb=None, Cb=None, *, dim, channel_last=True, softplus=True, **fields):
+    """The record of one direction - one parameter set in one time order over one xz - that both autograd nodes carry and the step
+    functions below read and fill.  xw / dtw: the x_proj / dt_proj weights as the projections take them (lowered by the node or
+    not); Bb / Cb: the projection biases; R / N: dt_rank, d_state; ns: nslices of this time order; w32 / cb32: the conv parameters
+    in fp32.  The steps add x_dbl, conv_out, delta, out, ckpt, chunk (forward), the scan parameters in fp32 (`_scan_f32`: the two
+    nodes make them at different points) and the backward's buffers dxz = (dx | dz), dx_dbl = (.. dBv | dCv ..)."""
+    return SimpleNamespace(conv_w=conv_w, conv_b=conv_b, xw=xw, dtw=dtw, A=A, D=D, dbias=dbias, Bb=Bb, Cb=Cb,
+                           R=dtw.shape[1], N=A.shape[-1], dim=dim, channel_last=channel_last, softplus=softplus,
+                           w32=conv_w.reshape(dim, -1).float().contiguous(),
+                           cb32=conv_b.float().contiguous() if conv_b is not None else None, **fields)
+
+
+_SAVED = ("conv_w", "conv_b", "x_dbl", "xw", "dtw", "A", "D", "dbias", "Bb", "Cb", "out", "ckpt", "conv_out", "delta")
+_GEOMETRY = ("batch", "seqlen", "dim", "channel_last", "order", "ns", "softplus", "chunk")
+
+
+def _for_backward(d, r, keep):
+    """With the forward scan's result r: -> the record's tensors for ctx.save_for_backward (the conv output and delta only when
+    the backward is not to recompute them), and the rest of what `_saved_direction` needs to build the record again"""
+    d.out, d.ckpt, d.chunk = r["out"], r["ckpt"], r["chunk"]
+    return ([None if f in ("conv_out", "delta") and not keep else getattr(d, f) for f in _SAVED],
+            {f: getattr(d, f) for f in _GEOMETRY})
+
+
+def _saved_direction(tensors, geometry):
+    d = _direction(**dict(zip(_SAVED, tensors)), **geometry)
+    d.rows_route = d.x_dbl.shape[1] != d.R + 2 * d.N        # the forward kept x_dbl padded: library projection route
+    return d
+
+
+def _scan_f32(d):
+    """the scan parameters in fp32.  Not made with the record: the nodes place these cast launches differently (`MambaInnerCore`
+    up front, `MambaInnerCore3` behind each direction's projections)"""
+    d.A32 = d.A.float().contiguous()
+    d.D32 = d.D.float().contiguous() if d.D is not None else None
+    d.db32 = d.dbias.float().contiguous() if d.dbias is not None else None
+
+
+def _conv1d_kw(d, x, **more):
+    """keyword set of the direction's conv1d + SiLU, forward or (with dout= and dx=) backward, single launch or `_multi` list"""
+    return dict(x=x, weight=d.w32, bias=d.cb32, silu=True, channel_last=d.channel_last, time_order=d.order, nslices=d.ns, **more)
+
+
+def _project_forward(d, conv_out, delta_in_scan=False):
+    """x_dbl and delta of the forward into the record, through the row-streaming kernel or BLAS -> B_t, C_t"""
+    d.conv_out = conv_out
+    if _rows_route(conv_out, d.channel_last) and d.Bb is None and d.Cb is None:
+        d.x_dbl, d.delta, Bv, Cv = _project_rows(conv_out, d.xw, d.dtw, d.R, d.N, delta_in_scan=delta_in_scan)
+    else:
+        d.x_dbl, d.delta, Bv, Cv = _project(conv_out, d.xw, d.dtw, d.R, d.N, d.channel_last, d.Bb, d.Cb)
+    return Bv, Cv
+
+
+def _scan_fwd_kw(d, Bv, Cv, z, train, dt_in_scan=False, conv_x=None):
+    """keyword set of the direction's forward scan (ops_raw.scan_fwd, or one entry of scan_fwd_multi's list), optionally with dt_proj
+    (`dt_in_scan`: the projection ran with `delta_in_scan`) or conv1d + SiLU (on `conv_x`, the conv1d input) inside the launches"""
+    # the un-gated y and the state checkpoints are only what the backward starts from: inference skips both stores.
+    # `train` is decided by the caller (_inner, Mamba.forward): ctx.needs_input_grad stays True for parameters under no_grad().
+    kw = dict(u=d.conv_out, delta=d.delta, A=d.A32, B=Bv, C=Cv, D=d.D32, z=z, delta_bias=d.db32, delta_softplus=d.softplus,
+              channel_last=d.channel_last, time_order=d.order, nslices=d.ns, need_out=train, need_ckpt=train)
+    if dt_in_scan:
+        kw.update(dt_x=d.x_dbl.view(d.batch, d.seqlen, -1)[:, :, :d.R],
+                  dt_weight=_pk(d.dtw, ("dt_proj_f32", d.R), lambda t: t.float().contiguous()))
+    if conv_x is not None:
+        # the north star's "conv1d fused into the scan launch": the passes read x and form u themselves (bit-identical).
+        # conv_out is still produced before - x_proj needs every channel of it before the scan can start - so this only
+        # moves work into the instruction-bound scan passes; measured slower, hence opt-in (DESIGN.md section 0, row N1)
+        kw.update(u=conv_x, conv_weight=d.conv_w.reshape(d.dim, -1), conv_bias=d.conv_b)
+    return kw
+
+
+def _backward_bc(d, lib, x):
+    """B_t / C_t for the backward: views of x_dbl where the forward kept the conv output and delta; else those two are recomputed
+    into the record (checkpoint_lvl 1)"""
+    if d.conv_out is not None:
+        return _bc_views(d.x_dbl, d.batch, d.seqlen, d.R, d.N, d.channel_last, d.Bb, d.Cb)
+    d.conv_out = ops_raw.conv1d_fwd(lib, **_conv1d_kw(d, x))
+    if d.rows_route:
+        _, d.delta, Bv, Cv = _project_rows(d.conv_out, d.xw, d.dtw, d.R, d.N, x_dbl=d.x_dbl)
+    else:
+        _, d.delta, Bv, Cv = _project(d.conv_out, d.xw, d.dtw, d.R, d.N, d.channel_last, d.Bb, d.Cb, x_dbl=d.x_dbl)
+    return Bv, Cv
+
+
+def _scan_bwd_buffers(d, xz):
+    d.dxz = torch.empty_like(xz, memory_format=torch.contiguous_format)
+    d.dx, d.dz = d.dxz.split(d.dim, dim=2 if d.channel_last else 1)         # dx / dz written in place (reference :244-245)
+    # dB / dC: offered the columns of the x_proj gradient operand as destinations (taken by the deterministic kernel)
+    d.dx_dbl, d.dBv, d.dCv = _dx_dbl_targets(d.x_dbl, d.batch, d.seqlen, d.R, d.N, d.channel_last)
+
+
+def _scan_bwd_kw(d, Bv, Cv, z, dout):
+    """keyword set of the direction's backward scan (ops_raw.scan_bwd, or one entry of scan_bwd_multi's list)"""
+    return dict(u=d.conv_out, delta=d.delta, A=d.A32, B=Bv, C=Cv, D=d.D32, z=z, delta_bias=d.db32, dout=dout, out=d.out,
+                ckpt=d.ckpt, delta_softplus=d.softplus, channel_last=d.channel_last, time_order=d.order, nslices=d.ns,
+                chunk=d.chunk, dz=d.dz, dB=d.dBv, dC=d.dCv)
+
+
+def _projection_grads(d, lib, g):
+    """From the scan backward's result g: -> (dx_proj_weight, ddelta_proj_weight, dconv2), dconv2 being the (b*l, d) gradient of
+    the conv output, the scan's share plus x_proj's.  The projection-bias gradients go into the record (d.dBb, d.dCb)."""
+    ddelta2, conv2, dconv2 = ((t if d.channel_last else t.permute(0, 2, 1)).reshape(d.batch * d.seqlen, d.dim)
+                              for t in (g["ddelta"], d.conv_out, g["du"]))      # (b*l, d) matrices
+    R, N, dx_dbl = d.R, d.N, d.dx_dbl
+    _dx_dbl_finish(dx_dbl, g, d.batch, d.seqlen, R, N, d.channel_last)
+    c0 = _bc_col(d.x_dbl, R, N)
+    d.dBb = dx_dbl[:, c0:c0 + N].float().sum(0).to(d.Bb.dtype) if d.Bb is not None else None
+    d.dCb = dx_dbl[:, c0 + N:c0 + 2 * N].float().sum(0).to(d.Cb.dtype) if d.Cb is not None else None
+    ddelta_proj_weight = tn_matmul(ddelta2, d.x_dbl[:, :R])                 # (d, R)    reference :272
+    if d.rows_route:
+        R4, P4, P8 = _rows_cols(R, N)
+        # (bl, R) = ddelta2 @ dt_proj_weight (reference :273), with the zero padding columns up to R4
+        ops_raw.linear_rows(lib, ddelta2, _pk(d.dtw, ("dt_proj_t_rows", R4), lambda t: _pad_rows(t.t(), R4)), out=dx_dbl[:, :R4])
+        dx_proj_weight = _x_proj_grad_rows(tn_matmul(dx_dbl[:, :P4], conv2), R, N)          # (R+2N, d) reference :275
+        wx_t = _pk(d.xw, ("x_proj_t4", P8), lambda t: _x_proj_rows4(t, R, N).t().contiguous())     # (d, P8)
+        dconv2 = ops_raw.linear_rows(lib, dx_dbl, wx_t, out=dconv2, accumulate=True)        # reference :276
+    else:
+        dx_dbl[:, :R] = ddelta2 @ d.dtw                                     # (bl, R)   reference :273
+        dx_proj_weight = tn_matmul(dx_dbl, conv2)                           # (R+2N, d) reference :275
+        dconv2 = torch.addmm(dconv2, dx_dbl, d.xw)                          # (bl, d)   reference :276
+    return dx_proj_weight, ddelta_proj_weight, dconv2
+
+
+def _cast_grads(d, g, dconv_w, dconv_b, dx_proj_weight, ddelta_proj_weight, xw_dtype, dtw_dtype):
+    """the direction's seven parameter gradients in the order of its parameters; the node says in which dtypes the projection weights' go back"""
+    return [dconv_w.reshape(d.conv_w.shape).to(d.conv_w.dtype), dconv_b.to(d.conv_b.dtype) if d.conv_b is not None else None,
+            dx_proj_weight.to(xw_dtype), ddelta_proj_weight.to(dtw_dtype), g["dA"].to(d.A.dtype),
+            g["dD"].to(d.D.dtype) if d.D is not None else None,
+            g["ddelta_bias"].to(d.dbias.dtype) if d.dbias is not None else None]
+
+
 class MambaInnerCore(torch.autograd.Function):
     """out_z = scan(silu(conv1d(x)), softplus(dt_proj(x_proj(.)) + bias), A, B(.), C(.), D) * silu(z).
 
@@ -187,120 +319,48 @@ class MambaInnerCore(torch.autograd.Function):
         cdim = 2 if channel_last else 1
         if (xz.stride(1) if channel_last else xz.stride(2)) != 1 and xz.stride(cdim) != 1:
             xz = xz.contiguous()
-        dim = xz.shape[cdim] // 2
-        R = delta_proj_weight.shape[1]
-        N = A.shape[-1]
         if A.is_complex():
             raise RuntimeError("complex A is not supported (not on the SegMamba path)")
-        w32 = conv1d_weight.reshape(dim, -1).float().contiguous()
-        cb32 = conv1d_bias.float().contiguous() if conv1d_bias is not None else None
-        A32 = A.float().contiguous()
-        D32 = D.float().contiguous() if D is not None else None
-        db32 = delta_bias.float().contiguous() if delta_bias is not None else None
-        x, z = xz.split(dim, dim=cdim)
-        conv_out = ops_raw.conv1d_fwd(lib, x, w32, cb32, True, channel_last=channel_last, time_order=time_order,
-                                      nslices=nslices)
-        if _rows_route(conv_out, channel_last) and B_proj_bias is None and C_proj_bias is None:
-            x_dbl, delta, Bv, Cv = _project_rows(conv_out, x_proj_weight, delta_proj_weight, R, N)
-        else:
-            x_dbl, delta, Bv, Cv = _project(conv_out, x_proj_weight, delta_proj_weight, R, N, channel_last,
-                                            B_proj_bias, C_proj_bias)
-        # the un-gated y and the state checkpoints are only what the backward starts from: inference skips both stores.
-        # `train` is decided by the caller (_inner): ctx.needs_input_grad stays True for parameters under no_grad().
-        r = ops_raw.scan_fwd(lib, conv_out, delta, A32, Bv, Cv, D32, z, db32, delta_softplus,
-                             channel_last=channel_last, time_order=time_order, nslices=nslices,
-                             need_out=train, need_ckpt=train)
-        keep = train and not _RECOMPUTE
-        ctx.cfg = (bool(delta_softplus), bool(channel_last), int(time_order), int(nslices), r["chunk"], R, N,
-                   B_proj_bias is not None, C_proj_bias is not None, keep)
-        ctx.save_for_backward(xz, conv1d_weight, conv1d_bias, x_dbl, x_proj_weight, delta_proj_weight, A, D,
-                              delta_bias, B_proj_bias, C_proj_bias, r["out"], r["ckpt"],
-                              conv_out if keep else None, delta if keep else None)
+        d = _direction(conv1d_weight, conv1d_bias, x_proj_weight, delta_proj_weight, A, D, delta_bias, B_proj_bias, C_proj_bias,
+                       batch=xz.shape[0], seqlen=xz.shape[1] if channel_last else xz.shape[2], dim=xz.shape[cdim] // 2,
+                       channel_last=bool(channel_last), order=int(time_order), ns=int(nslices), softplus=bool(delta_softplus))
+        _scan_f32(d)
+        x, z = xz.split(d.dim, dim=cdim)
+        Bv, Cv = _project_forward(d, ops_raw.conv1d_fwd(lib, **_conv1d_kw(d, x)))
+        r = ops_raw.scan_fwd(lib, **_scan_fwd_kw(d, Bv, Cv, z, train))
+        tensors, ctx.geometry = _for_backward(d, r, keep=train and not _RECOMPUTE)
+        ctx.save_for_backward(xz, *tensors)
         return r["out_z"]
 
     @staticmethod
     @_custom_bwd
     def backward(ctx, dout):
         lib = L.get_lib()
-        (xz, conv1d_weight, conv1d_bias, x_dbl, x_proj_weight, delta_proj_weight, A, D, delta_bias,
-         B_proj_bias, C_proj_bias, out, ckpt, conv_out, delta) = ctx.saved_tensors
-        delta_softplus, channel_last, time_order, nslices, chunk, R, N, has_Bb, has_Cb, keep = ctx.cfg
-        cdim = 2 if channel_last else 1
-        dim = xz.shape[cdim] // 2
-        batch = xz.shape[0]
-        seqlen = xz.shape[1] if channel_last else xz.shape[2]
-        w32 = conv1d_weight.reshape(dim, -1).float().contiguous()
-        cb32 = conv1d_bias.float().contiguous() if conv1d_bias is not None else None
-        A32 = A.float().contiguous()
-        D32 = D.float().contiguous() if D is not None else None
-        db32 = delta_bias.float().contiguous() if delta_bias is not None else None
-        x, z = xz.split(dim, dim=cdim)
-        if (dout.stride(1) if channel_last else dout.stride(2)) != 1 and dout.stride(cdim) != 1:
+        xz, *tensors = ctx.saved_tensors
+        d = _saved_direction(tensors, ctx.geometry)
+        cdim = 2 if d.channel_last else 1
+        _scan_f32(d)
+        x, z = xz.split(d.dim, dim=cdim)
+        if (dout.stride(1) if d.channel_last else dout.stride(2)) != 1 and dout.stride(cdim) != 1:
             dout = dout.contiguous()
-        rows_route = x_dbl.shape[1] != R + 2 * N           # the forward kept x_dbl padded: library projection route
-        if keep:                                           # conv output and delta kept by the forward: B / C are views of x_dbl
-            Bv, Cv = _bc_views(x_dbl, batch, seqlen, R, N, channel_last, B_proj_bias, C_proj_bias)
-        else:                                              # recompute them (checkpoint_lvl 1)
-            conv_out = ops_raw.conv1d_fwd(lib, x, w32, cb32, True, channel_last=channel_last, time_order=time_order,
-                                          nslices=nslices)
-            if rows_route:
-                _, delta, Bv, Cv = _project_rows(conv_out, x_proj_weight, delta_proj_weight, R, N, x_dbl=x_dbl)
-            else:
-                _, delta, Bv, Cv = _project(conv_out, x_proj_weight, delta_proj_weight, R, N, channel_last,
-                                            B_proj_bias, C_proj_bias, x_dbl=x_dbl)
-        dxz = torch.empty_like(xz, memory_format=torch.contiguous_format)
-        dx, dz = dxz.split(dim, dim=cdim)                 # dx / dz written in place (reference :244-245)
-        # dB / dC: offered the columns of the x_proj gradient operand as destinations (taken by the deterministic kernel)
-        dx_dbl, dBv, dCv = _dx_dbl_targets(x_dbl, batch, seqlen, R, N, channel_last)
-        g = ops_raw.scan_bwd(lib, conv_out, delta, A32, Bv, Cv, D32, z, db32, dout, out, ckpt, delta_softplus,
-                             channel_last=channel_last, time_order=time_order, nslices=nslices, chunk=chunk, dz=dz,
-                             dB=dBv, dC=dCv)
-        dconv_out, ddelta = g["du"], g["ddelta"]
-        # (b*l, .) matrices for the projection gradients
-        if channel_last:
-            ddelta2 = ddelta.reshape(batch * seqlen, dim)                       # (bl, d)
-            conv2 = conv_out.reshape(batch * seqlen, dim)
-            dconv2 = dconv_out.reshape(batch * seqlen, dim)
-        else:
-            ddelta2 = ddelta.permute(0, 2, 1).reshape(batch * seqlen, dim)
-            conv2 = conv_out.permute(0, 2, 1).reshape(batch * seqlen, dim)
-            dconv2 = dconv_out.permute(0, 2, 1).reshape(batch * seqlen, dim)
-        _dx_dbl_finish(dx_dbl, g, batch, seqlen, R, N, channel_last)
-        c0 = _bc_col(x_dbl, R, N)
-        dB_proj_bias = dx_dbl[:, c0:c0 + N].float().sum(0).to(B_proj_bias.dtype) if has_Bb else None
-        dC_proj_bias = dx_dbl[:, c0 + N:c0 + 2 * N].float().sum(0).to(C_proj_bias.dtype) if has_Cb else None
-        ddelta_proj_weight = tn_matmul(ddelta2, x_dbl[:, :R])                   # (d, R)    reference :272
-        if rows_route:
-            R4, P4, P8 = _rows_cols(R, N)
-            # (bl, R) = ddelta2 @ dt_proj_weight (reference :273), with the zero padding columns up to R4
-            ops_raw.linear_rows(lib, ddelta2, _pk(delta_proj_weight, ("dt_proj_t_rows", R4), lambda t: _pad_rows(t.t(), R4)), out=dx_dbl[:, :R4])
-            dx_proj_weight = _x_proj_grad_rows(tn_matmul(dx_dbl[:, :P4], conv2), R, N)          # (R+2N, d) reference :275
-            wx_t = _pk(x_proj_weight, ("x_proj_t4", P8), lambda t: _x_proj_rows4(t, R, N).t().contiguous())     # (d, P8)
-            dconv2 = ops_raw.linear_rows(lib, dx_dbl, wx_t, out=dconv2, accumulate=True)        # reference :276
-        else:
-            dx_dbl[:, :R] = ddelta2 @ delta_proj_weight                         # (bl, R)   reference :273
-            dx_proj_weight = tn_matmul(dx_dbl, conv2)                          # (R+2N, d) reference :275
-            dconv2 = torch.addmm(dconv2, dx_dbl, x_proj_weight)                 # (bl, d)   reference :276
-        dconv_full = dconv2.reshape(batch, seqlen, dim)
-        if not channel_last:
+        Bv, Cv = _backward_bc(d, lib, x)
+        _scan_bwd_buffers(d, xz)
+        g = ops_raw.scan_bwd(lib, **_scan_bwd_kw(d, Bv, Cv, z, dout))
+        dx_proj_weight, ddelta_proj_weight, dconv2 = _projection_grads(d, lib, g)
+        dconv_full = dconv2.reshape(d.batch, d.seqlen, d.dim)
+        if not d.channel_last:
             dconv_full = dconv_full.permute(0, 2, 1)                             # strided (b, d, l) view
-        _, dconv_w, dconv_b = ops_raw.conv1d_bwd(lib, x, w32, cb32, dconv_full, True, channel_last=channel_last,
-                                                 time_order=time_order, nslices=nslices, dx=dx)
-        dconv_w = dconv_w.reshape(conv1d_weight.shape).to(conv1d_weight.dtype)
-        dconv_b = dconv_b.to(conv1d_bias.dtype) if conv1d_bias is not None else None
-        return (dxz, dconv_w, dconv_b, dx_proj_weight.to(x_proj_weight.dtype),
-                ddelta_proj_weight.to(delta_proj_weight.dtype), g["dA"].to(A.dtype),
-                g["dD"].to(D.dtype) if D is not None else None,
-                g["ddelta_bias"].to(delta_bias.dtype) if delta_bias is not None else None,
-                dB_proj_bias, dC_proj_bias, None, None, None, None, None)
+        _, dconv_w, dconv_b = ops_raw.conv1d_bwd(lib, **_conv1d_kw(d, x, dout=dconv_full, dx=d.dx))
+        grads = _cast_grads(d, g, dconv_w, dconv_b, dx_proj_weight, ddelta_proj_weight, d.xw.dtype, d.dtw.dtype)   # as the forward took them
+        return (d.dxz, *grads, d.dBb, d.dCb, None, None, None, None, None)
 
 
 class MambaInnerCore3(torch.autograd.Function):
     """The three directions of a `Mamba(bimamba_type="v3")` layer as ONE autograd node (reference mamba_simple.py:216-264 calls
     `mamba_inner_fn_no_out_proj` three times: as stored, time-reversed, slice-interleaved - three parameter sets on one `xz`).
 
-    Same arithmetic per direction as `MambaInnerCore` on channel-last tensors; what the node buys is launch structure: the three
-    selective scans of the forward (and of the backward) are ONE grid with a direction axis
+    Per direction the same steps as `MambaInnerCore` on channel-last tensors (the module-level functions above); what the node
+    buys is launch structure: the three selective scans of the forward (and of the backward) are ONE grid with a direction axis
     (`segm_selective_scan_{fwd,bwd}_multi`) - 3 x the waves where one direction cannot fill the 1024 SIMDs (stages 1 - 3:
     12.6 M, 3.1 M, 0.8 M channel-steps) and a third of the scan launches - and the three `dxz` contributions are summed inside
     the node.  Arguments: xz (B, L, 2D), nslices, train, then for each direction (conv1d_weight, conv1d_bias, x_proj_weight,
@@ -313,7 +373,6 @@ class MambaInnerCore3(torch.autograd.Function):
     def forward(ctx, xz, nslices, train, *params):
         lib = L.get_lib()
         assert len(params) == 21
-        sets = [params[7 * i:7 * i + 7] for i in range(3)]
         # 16-bit activations with fp32 master weights (autocast, or a caller that feeds 16-bit tokens): the projections take the
         # step's 16-bit copies of the masters (param_bank.low_precision), their gradients go back in fp32
         act_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else (
@@ -324,124 +383,61 @@ class MambaInnerCore3(torch.autograd.Function):
         dim = dim2 // 2
         x, z = xz.split(dim, dim=2)
         keep = train and not _RECOMPUTE
-        calls, per_dir = [], []
-        conv_outs = ops_raw.conv1d_fwd_multi(lib, [
-            dict(x=x, weight=st[0].reshape(dim, -1).float().contiguous(), bias=st[1].float().contiguous() if st[1] is not None else None,
-                 silu=True, channel_last=True, time_order=MambaInnerCore3.ORDERS[i],
-                 nslices=nslices if MambaInnerCore3.ORDERS[i] == L.TIME_INTERLEAVED else 1) for i, st in enumerate(sets)])
-        for i, (conv_w, conv_b, xw, dtw, A, D, dbias) in enumerate(sets):
-            if act_dtype is not None and xw.dtype != act_dtype:
+        dirs = [_direction(*params[7 * i:7 * i + 7], batch=batch, seqlen=seqlen, dim=dim, order=order,
+                           ns=nslices if order == L.TIME_INTERLEAVED else 1) for i, order in enumerate(MambaInnerCore3.ORDERS)]
+        ctx.master_dtypes = [(d.xw.dtype, d.dtw.dtype) for d in dirs]       # weight gradients go back in them
+        conv_outs = ops_raw.conv1d_fwd_multi(lib, [_conv1d_kw(d, x) for d in dirs])
+        calls = []
+        for d, conv_out in zip(dirs, conv_outs):
+            if act_dtype is not None and d.xw.dtype != act_dtype:
                 from .param_bank import low_precision
-                xw, dtw = low_precision(xw, act_dtype), low_precision(dtw, act_dtype)
-            R, N = dtw.shape[1], A.shape[-1]
-            ns = nslices if MambaInnerCore3.ORDERS[i] == L.TIME_INTERLEAVED else 1
-            conv_out = conv_outs[i]
+                d.xw, d.dtw = low_precision(d.xw, act_dtype), low_precision(d.dtw, act_dtype)
             # dt_proj inside the scan launches (opt-in): the stored-delta forms only (with recompute the backward would form delta
             # through the other kernel and the two roundings could differ by an ulp of the 16-bit type)
-            dt_in_scan = _FUSED_DTPROJ and not _FUSED_CONV1D and R <= 8 and _rows_route(conv_out, True) and (keep or not train) and \
-                ops_raw.scan_fused_conv_supported(lib, batch, dim, seqlen, ns, MambaInnerCore3.ORDERS[i])
-            if _rows_route(conv_out, True):
-                x_dbl, delta, Bv, Cv = _project_rows(conv_out, xw, dtw, R, N, delta_in_scan=dt_in_scan)
-            else:
-                x_dbl, delta, Bv, Cv = _project(conv_out, xw, dtw, R, N, True, None, None)
-            calls.append(dict(u=conv_out, delta=delta, A=A.float().contiguous(), B=Bv, C=Cv,
-                              D=D.float().contiguous() if D is not None else None, z=z,
-                              delta_bias=dbias.float().contiguous() if dbias is not None else None, delta_softplus=True,
-                              channel_last=True, time_order=MambaInnerCore3.ORDERS[i], nslices=ns, need_out=train, need_ckpt=train))
-            if dt_in_scan:
-                calls[-1].update(dt_x=x_dbl.view(batch, seqlen, -1)[:, :, :R],
-                                 dt_weight=_pk(dtw, ("dt_proj_f32", R), lambda t: t.float().contiguous()))
-            if _FUSED_CONV1D and ops_raw.scan_fused_conv_supported(lib, batch, dim, seqlen, ns, calls[-1]["time_order"]):
-                # the north star's "conv1d fused into the scan launch": the passes read x and form u themselves (bit-identical).
-                # conv_out is still produced above - x_proj needs every channel of it before the scan can start - so this only
-                # moves work into the instruction-bound scan passes; measured slower, hence opt-in
-                calls[-1].update(u=x, conv_weight=conv_w.reshape(dim, -1), conv_bias=conv_b)
-            per_dir.append((x_dbl, xw, dtw, conv_out, delta, R, N, ns))
+            dt_in_scan = bool(_FUSED_DTPROJ and not _FUSED_CONV1D and d.R <= 8 and _rows_route(conv_out, True) and (keep or not train)
+                              and ops_raw.scan_fused_conv_supported(lib, batch, dim, seqlen, d.ns, d.order))
+            Bv, Cv = _project_forward(d, conv_out, delta_in_scan=dt_in_scan)
+            _scan_f32(d)
+            conv_in_scan = _FUSED_CONV1D and ops_raw.scan_fused_conv_supported(lib, batch, dim, seqlen, d.ns, d.order)
+            calls.append(_scan_fwd_kw(d, Bv, Cv, z, train, dt_in_scan=dt_in_scan, conv_x=x if conv_in_scan else None))
         rs = ops_raw.scan_fwd_multi(lib, calls)
-        saved = [xz]
-        for (conv_w, conv_b, xw0, dtw0, A, D, dbias), (x_dbl, xw, dtw, conv_out, delta, R, N, ns), r in zip(sets, per_dir, rs):
-            saved += [conv_w, conv_b, x_dbl, xw, dtw, A, D, dbias, r["out"], r["ckpt"],
-                      conv_out if keep else None, delta if keep else None]
-        ctx.cfg = (int(nslices), [r["chunk"] for r in rs], [(p[5], p[6]) for p in per_dir], keep,
-                   [(st[2].dtype, st[3].dtype) for st in sets])         # the masters' dtypes: weight gradients go back in them
-        ctx.save_for_backward(*saved)
+        saved = [_for_backward(d, r, keep) for d, r in zip(dirs, rs)]
+        ctx.geometry = [geometry for _, geometry in saved]
+        ctx.save_for_backward(xz, *(t for tensors, _ in saved for t in tensors))
         return tuple(r["out_z"] for r in rs)
 
     @staticmethod
     @_custom_bwd
     def backward(ctx, *douts):
         lib = L.get_lib()
-        nslices, chunks, rn, keep, wdt = ctx.cfg
-        saved = ctx.saved_tensors
-        xz = saved[0]
-        batch, seqlen, dim2 = xz.shape
-        dim = dim2 // 2
-        x, z = xz.split(dim, dim=2)
-        dirs, calls = [], []
-        for i in range(3):
-            (conv_w, conv_b, x_dbl, xw, dtw, A, D, dbias, out, ckpt, conv_out, delta) = saved[1 + 12 * i:13 + 12 * i]
-            R, N = rn[i]
-            order = MambaInnerCore3.ORDERS[i]
-            ns = nslices if order == L.TIME_INTERLEAVED else 1
-            w32 = conv_w.reshape(dim, -1).float().contiguous()
-            cb32 = conv_b.float().contiguous() if conv_b is not None else None
-            rows_route = x_dbl.shape[1] != R + 2 * N
-            if keep:
-                Bv, Cv = _bc_views(x_dbl, batch, seqlen, R, N, True, None, None)
-            else:
-                conv_out = ops_raw.conv1d_fwd(lib, x, w32, cb32, True, channel_last=True, time_order=order, nslices=ns)
-                if rows_route:
-                    _, delta, Bv, Cv = _project_rows(conv_out, xw, dtw, R, N, x_dbl=x_dbl)
-                else:
-                    _, delta, Bv, Cv = _project(conv_out, xw, dtw, R, N, True, None, None, x_dbl=x_dbl)
-            dout = douts[i]
+        xz, *tensors = ctx.saved_tensors
+        x, z = xz.split(xz.shape[2] // 2, dim=2)
+        n, dirs, calls = len(_SAVED), [], []
+        for i, (geometry, dout) in enumerate(zip(ctx.geometry, douts)):
+            d = _saved_direction(tensors[n * i:n * (i + 1)], geometry)
+            Bv, Cv = _backward_bc(d, lib, x)
             if dout.stride(2) != 1:
                 dout = dout.contiguous()
-            dxz = torch.empty_like(xz, memory_format=torch.contiguous_format)
-            dx, dz = dxz.split(dim, dim=2)
-            dx_dbl, dBv, dCv = _dx_dbl_targets(x_dbl, batch, seqlen, R, N, True)
-            calls.append(dict(u=conv_out, delta=delta, A=A.float().contiguous(), B=Bv, C=Cv,
-                              D=D.float().contiguous() if D is not None else None, z=z,
-                              delta_bias=dbias.float().contiguous() if dbias is not None else None, dout=dout, out=out, ckpt=ckpt,
-                              delta_softplus=True, channel_last=True, time_order=order, nslices=ns, chunk=chunks[i], dz=dz,
-                              dB=dBv, dC=dCv))
-            dirs.append((conv_w, conv_b, x_dbl, xw, dtw, A, D, dbias, conv_out, R, N, order, ns, w32, cb32, rows_route, dxz, dx, dx_dbl))
+            _scan_bwd_buffers(d, xz)
+            _scan_f32(d)
+            calls.append(_scan_bwd_kw(d, Bv, Cv, z, dout))
+            dirs.append(d)
         gs = ops_raw.scan_bwd_multi(lib, calls)
-        grads, dxz_sum, ccalls, part = [], None, [], []
-        for i, ((conv_w, conv_b, x_dbl, xw, dtw, A, D, dbias, conv_out, R, N, order, ns, w32, cb32, rows_route, dxz, dx, dx_dbl), g) in enumerate(zip(dirs, gs)):
-            dconv2 = g["du"].reshape(batch * seqlen, dim)
-            ddelta2 = g["ddelta"].reshape(batch * seqlen, dim)
-            conv2 = conv_out.reshape(batch * seqlen, dim)
-            _dx_dbl_finish(dx_dbl, g, batch, seqlen, R, N, True)
-            ddelta_proj_weight = tn_matmul(ddelta2, x_dbl[:, :R])
-            if rows_route:
-                R4, P4, P8 = _rows_cols(R, N)
-                ops_raw.linear_rows(lib, ddelta2, _pk(dtw, ("dt_proj_t_rows", R4), lambda t: _pad_rows(t.t(), R4)), out=dx_dbl[:, :R4])
-                dx_proj_weight = _x_proj_grad_rows(tn_matmul(dx_dbl[:, :P4], conv2), R, N)
-                wx_t = _pk(xw, ("x_proj_t4", P8), lambda t: _x_proj_rows4(t, R, N).t().contiguous())
-                dconv2 = ops_raw.linear_rows(lib, dx_dbl, wx_t, out=dconv2, accumulate=True)
-            else:
-                dx_dbl[:, :R] = ddelta2 @ dtw
-                dx_proj_weight = tn_matmul(dx_dbl, conv2)
-                dconv2 = torch.addmm(dconv2, dx_dbl, xw)
-            ccalls.append(dict(x=x, weight=w32, bias=cb32, dout=dconv2.reshape(batch, seqlen, dim), silu=True, channel_last=True,
-                               time_order=order, nslices=ns, dx=dx))
+        ccalls, part = [], []
+        for d, g in zip(dirs, gs):
+            dx_proj_weight, ddelta_proj_weight, dconv2 = _projection_grads(d, lib, g)
+            ccalls.append(_conv1d_kw(d, x, dout=dconv2.reshape(d.batch, d.seqlen, d.dim), dx=d.dx))
             part.append((dx_proj_weight, ddelta_proj_weight))
         cres = ops_raw.conv1d_bwd_multi(lib, ccalls)
         # the three dxz contributions: one pass a + b + c (segm_add3) instead of two in-place binary adds (SEGM_ADD3=0: those)
-        all_dxz = [d[16] for d in dirs]
+        all_dxz = [d.dxz for d in dirs]
         use3 = _ADD3 and len(all_dxz) == 3 and ops_raw.add3_supported(*all_dxz)
-        if use3:
-            dxz_sum = ops_raw.add3(lib, *all_dxz, out=all_dxz[0])
-        for i, ((conv_w, conv_b, x_dbl, xw, dtw, A, D, dbias, conv_out, R, N, order, ns, w32, cb32, rows_route, dxz, dx, dx_dbl), g) in enumerate(zip(dirs, gs)):
-            _, dconv_w, dconv_b = cres[i]
-            dx_proj_weight, ddelta_proj_weight = part[i]
+        dxz_sum = ops_raw.add3(lib, *all_dxz, out=all_dxz[0]) if use3 else None
+        grads = []
+        for d, g, (_, dconv_w, dconv_b), (dx_proj_weight, ddelta_proj_weight), master in zip(dirs, gs, cres, part, ctx.master_dtypes):
             if not use3:
-                dxz_sum = dxz if dxz_sum is None else dxz_sum.add_(dxz)
-            grads += [dconv_w.reshape(conv_w.shape).to(conv_w.dtype), dconv_b.to(conv_b.dtype) if conv_b is not None else None,
-                      dx_proj_weight.to(wdt[i][0]), ddelta_proj_weight.to(wdt[i][1]), g["dA"].to(A.dtype),
-                      g["dD"].to(D.dtype) if D is not None else None,
-                      g["ddelta_bias"].to(dbias.dtype) if dbias is not None else None]
+                dxz_sum = d.dxz if dxz_sum is None else dxz_sum.add_(d.dxz)
+            grads += _cast_grads(d, g, dconv_w, dconv_b, dx_proj_weight, ddelta_proj_weight, *master)
         return (dxz_sum, None, None, *grads)
 
 
