@@ -1547,6 +1547,74 @@ int segm_intensity_stats(const segm_intensity_args* args);
 int segm_intensity_apply(const segm_intensity_args* args);
 
 
+/* ------------------------------------------------------------------------------------------------
+ * Stitching a sliding-window prediction (additive to ABI 10; csrc/stitch.hip): the window gather, the count map, the weighted
+ * blending and the close of a mirror pass, in place of the ATen chain around the network in segmamba_amd/predictor.py - the
+ * reference's monai/inferers/utils.py sliding_window_inference (pad, slice + cat, cast, multiply, slice-add, divide, crop) and the
+ * mirror loop of light_training/prediction.py:110-159 (torch.flip of the input and of every result, the running sum, the mean).
+ * Geometry, as sliding_window_inference defines it: the volume (batch, channels, size z, y, x) fp32; per axis
+ * image = max(size, roi) and pad0 = (image - size) / 2 (the volume is centred in the padded frame, the odd voxel behind it); a
+ * window is (sample, start z, y, x) with 0 <= start <= image - roi in the padded frame.  mirror: bit 0 flips z, bit 1 flips y,
+ * bit 2 flips x - the convention of segm_intensity_args.  The flip and the padding are folded into the index: neither a mirrored
+ * nor a padded copy exists.  A launch carries 1 .. SEGM_STITCH_MAX_WINDOWS windows by value; a caller with more splits the list
+ * and keeps its order.
+ *   segm_window_gather   windows_out (n_windows, channels, roi) fp32 dense.  Window voxel i along an axis has the padded-frame
+ *                        coordinate q = start + i and u = q - pad0: cval where u is outside [0, size), otherwise the volume at
+ *                        size - 1 - u (flipped axis) or u.  The volume has element strides for sample, channel, z and y and a unit
+ *                        stride along x.
+ *   segm_window_count    count (image) fp32 from weight (roi) fp32 dense and the start lists of the three axes: per voxel the
+ *                        weights of the covering windows added in the order of the lists' product (z outermost, x fastest), from 0 -
+ *                        the bits of the loop `count[slice] += weight`.
+ *   segm_window_blend    acc[sample, :, start + i] += fl32(float(pred[n, :, i]) * weight[i]) for the windows of the launch; acc
+ *                        (batch, channels, image) fp32 dense, pred (n_windows, channels, roi) dense in `dtype`.  The product is
+ *                        rounded on its own; the additions to one voxel happen in window order; every voxel of acc has one writer
+ *                        (a thread takes voxels of acc and walks the windows that cover them), no atomics.
+ *   segm_window_finish   closes pass `pass` of `passes`: for every voxel v of total (batch, channels, size) fp32 dense, with
+ *                        p = pad0 + (flipped ? size - 1 - v : v) and q = acc[p] / count[p] (fp32, correctly rounded):
+ *                        total = q for pass 0, total + q later; the last pass then divides by `passes`.  acc is all zero afterwards
+ *                        (the kernel stores zeros where it has read; the border of a padded image, which it does not read, is
+ *                        zeroed by a memset on the same stream).  passes = 1, mirror = 0: acc / count without the centring padding.
+ * A thread takes four voxels along x: as one packet of 16 bytes where they are whole and aligned, voxel by voxel otherwise; an
+ * x-flip reverses the packet; both routes call the same per-voxel function.  No floating-point atomics: two calls are bit-equal.
+ * Refused with nothing launched: n_windows outside [1, SEGM_STITCH_MAX_WINDOWS], a start list outside [1, SEGM_STITCH_MAX_STARTS],
+ * batch, channels or a side < 1, 2^31 voxels per image plane or more, n_windows * channels (blend, finish: batch * channels) > 65535, a
+ * window or a start that leaves the image, a sample outside [0, batch), stride_x != 1, a negative stride, a mirror outside 0 .. 7,
+ * pass outside [0, passes), a pointer not aligned to its element (SEGM_E_SHAPE); an unknown dtype (SEGM_E_DTYPE); a required
+ * pointer that is NULL (SEGM_E_NULL).
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_STITCH_MAX_WINDOWS 64
+#define SEGM_STITCH_MAX_STARTS 64
+
+typedef struct segm_stitch_args {
+    int32_t batch, channels;                              /* of volume (gather); of acc, pred and total (blend, finish) */
+    int32_t size[3];                                      /* z, y, x of the volume / of total */
+    int32_t roi[3];
+    int32_t n_windows;                                    /* gather, blend */
+    int32_t mirror;                                       /* gather, finish */
+    int32_t dtype;                                        /* blend: of pred, SEGM_F32 / SEGM_F16 / SEGM_BF16 */
+    int32_t pass, passes;                                 /* finish */
+    float cval;                                           /* gather: the padding value */
+    int32_t n_starts[3];                                  /* count */
+    int32_t reserved;
+    int32_t window[SEGM_STITCH_MAX_WINDOWS][4];           /* gather, blend: sample, start z, y, x */
+    int32_t starts[3][SEGM_STITCH_MAX_STARTS];            /* count: the window starts of each axis, in order */
+    int64_t stride_b, stride_c, stride_z, stride_y, stride_x;              /* gather: of volume */
+    const float* volume;                                  /* gather */
+    float* windows_out;                                   /* gather */
+    const float* weight;                                  /* count, blend */
+    float* count;                                         /* count: written; finish: read */
+    const void* pred;                                     /* blend */
+    float* acc;                                           /* blend: accumulated into; finish: read, then zeroed */
+    float* total;                                         /* finish */
+    void* stream;
+} segm_stitch_args;
+
+int segm_window_gather(const segm_stitch_args* args);
+int segm_window_count(const segm_stitch_args* args);
+int segm_window_blend(const segm_stitch_args* args);
+int segm_window_finish(const segm_stitch_args* args);
+
+
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);
 const char* segm_status_string(int status);

@@ -309,6 +309,7 @@ EXPORTS = (
     "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
     "segm_gauss_blur",
     "segm_intensity_workspace_bytes", "segm_intensity_stats", "segm_intensity_apply",
+    "segm_window_gather", "segm_window_count", "segm_window_blend", "segm_window_finish",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -568,6 +569,20 @@ class IntensityArgs(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
+STITCH_MAX_WINDOWS, STITCH_MAX_STARTS = 64, 64                                  # SEGM_STITCH_MAX_*
+
+
+class StitchArgs(C.Structure):
+    _fields_ = [("batch", C.c_int32), ("channels", C.c_int32), ("size", C.c_int32 * 3), ("roi", C.c_int32 * 3),
+                ("n_windows", C.c_int32), ("mirror", C.c_int32), ("dtype", C.c_int32), ("pass_", C.c_int32), ("passes", C.c_int32),
+                ("cval", C.c_float), ("n_starts", C.c_int32 * 3), ("reserved", C.c_int32),
+                ("window", (C.c_int32 * 4) * STITCH_MAX_WINDOWS), ("starts", (C.c_int32 * STITCH_MAX_STARTS) * 3),
+                ("stride_b", C.c_int64), ("stride_c", C.c_int64), ("stride_z", C.c_int64), ("stride_y", C.c_int64),
+                ("stride_x", C.c_int64),
+                ("volume", C.c_void_p), ("windows_out", C.c_void_p), ("weight", C.c_void_p), ("count", C.c_void_p),
+                ("pred", C.c_void_p), ("acc", C.c_void_p), ("total", C.c_void_p), ("stream", C.c_void_p)]
+
+
 def header_abi_version() -> int:
     """SEGM_ABI_VERSION as include/segmamba_hip.h declares it (what a freshly built library must report)"""
     import re
@@ -693,6 +708,8 @@ class SegmLib:
         sig("segm_intensity_workspace_bytes", [C.c_int32, C.c_int64], C.c_size_t)
         sig("segm_intensity_stats", [C.POINTER(IntensityArgs)], C.c_int)
         sig("segm_intensity_apply", [C.POINTER(IntensityArgs)], C.c_int)
+        for n in ("segm_window_gather", "segm_window_count", "segm_window_blend", "segm_window_finish"):
+            sig(n, [C.POINTER(StitchArgs)], C.c_int)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

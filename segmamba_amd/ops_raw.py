@@ -2549,6 +2549,166 @@ def intensity_apply(lib: L.SegmLib, x: torch.Tensor, ops, stats: torch.Tensor = 
 
 
 # ---------------------------------------------------------------------------------------------------------
+# stitching a sliding-window prediction (csrc/stitch.hip): window gather, count map, blending, the close of a mirror pass.  The
+# windows of a launch travel by value in the argument struct; nothing is read back to the host.
+# ---------------------------------------------------------------------------------------------------------
+def _stitch_sides(size, roi, what: str):
+    """-> (size, roi, image = max(size, roi)) as tuples of 3 ints"""
+    try:
+        size, roi = tuple(int(v) for v in size), tuple(int(v) for v in roi)
+    except (TypeError, ValueError):
+        raise RuntimeError(f"{what}: three integer sides each for size and roi are required, got {size!r} and {roi!r}") from None
+    if len(size) != 3 or len(roi) != 3 or min(size + roi) < 1:
+        raise RuntimeError(f"{what}: three sides of at least 1 each for size and roi are required, got {size} and {roi}")
+    image = tuple(max(s, r) for s, r in zip(size, roi))
+    if image[0] * image[1] * image[2] >= 2 ** 31:
+        raise RuntimeError(f"{what}: fewer than 2^31 voxels per plane are required, got {image}")
+    return size, roi, image
+
+
+def _stitch_dense(t, shape, dtypes, like, what: str) -> None:
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape) or t.dtype not in dtypes or not t.is_contiguous() \
+            or (like is not None and t.device != like.device) or t.data_ptr() % t.element_size():
+        where = f" on {like.device}" if like is not None else ""
+        raise RuntimeError(f"{what}: a contiguous tensor {tuple(shape)} of {' / '.join(str(d) for d in dtypes)}{where} is required, got "
+                           f"{getattr(t, 'shape', type(t))} {getattr(t, 'dtype', '')} {getattr(t, 'device', '')}")
+
+
+def _stitch_windows(a, windows, batch: int, channels: int, image, roi, what: str) -> int:
+    windows = [tuple(w) for w in windows]
+    if not 1 <= len(windows) <= L.STITCH_MAX_WINDOWS:
+        raise RuntimeError(f"{what}: 1 .. {L.STITCH_MAX_WINDOWS} windows per launch are required, got {len(windows)}")
+    if len(windows) * channels > 65535:
+        raise RuntimeError(f"{what}: windows x channels must not exceed 65535, got {len(windows)} x {channels}")
+    for j, w in enumerate(windows):
+        if len(w) != 4 or any(int(v) != v for v in w):
+            raise RuntimeError(f"{what}: window {j}: (sample, start z, y, x) integers are required, got {w!r}")
+        if not 0 <= w[0] < batch or any(not 0 <= w[1 + d] <= image[d] - roi[d] for d in range(3)):
+            raise RuntimeError(f"{what}: window {j} = {w} leaves the {batch} samples of the image {tuple(image)} (roi {tuple(roi)})")
+        for d in range(4):
+            a.window[j][d] = int(w[d])
+    a.n_windows = len(windows)
+    return len(windows)
+
+
+def _stitch_mirror(mirror, what: str) -> int:
+    if isinstance(mirror, bool) or not isinstance(mirror, int) or not 0 <= mirror <= 7:
+        raise RuntimeError(f"{what}: a mirror mask in 0 .. 7 is required (1: flip z, 2: flip y, 4: flip x), got {mirror!r}")
+    return mirror
+
+
+def window_gather(lib: L.SegmLib, volume: torch.Tensor, roi, windows, mirror: int = 0, cval: float = 0.0) -> torch.Tensor:
+    """volume (B, C, Z, Y, X) fp32 with a unit stride along x (other strides free), `windows` 1 .. 64 tuples (sample, start z, y, x)
+    in the padded frame image = max(size, roi) -> (n, C, *roi) fp32 dense: the volume mirrored by `mirror` and centred in the
+    padding `cval`, cut at the windows.  Neither the mirrored nor the padded volume is formed."""
+    what = "window_gather"
+    if not isinstance(volume, torch.Tensor) or volume.dim() != 5:
+        raise RuntimeError(f"{what}: a volume (B, C, Z, Y, X) is required, got {getattr(volume, 'shape', type(volume))}")
+    if volume.dtype != torch.float32:
+        raise RuntimeError(f"{what}: a float32 volume is required, got {volume.dtype}")
+    B, C_ = int(volume.shape[0]), int(volume.shape[1])
+    if B < 1 or C_ < 1:
+        raise RuntimeError(f"{what}: at least one sample and one channel are required, got {tuple(volume.shape)}")
+    size, roi, image = _stitch_sides(volume.shape[2:], roi, what)
+    sb, sc, sz, sy, sx = volume.stride()
+    if size[2] > 1 and sx != 1:
+        raise RuntimeError(f"{what}: the volume needs a unit stride along the last dimension, got strides {volume.stride()}")
+    if min(sb, sc, sz, sy) < 0 or volume.data_ptr() % 4:
+        raise RuntimeError(f"{what}: unsupported volume strides {volume.stride()} or a misaligned base")
+    cval = float(cval)
+    a = L.StitchArgs()
+    n = _stitch_windows(a, windows, B, C_, image, roi, what)
+    a.mirror = _stitch_mirror(mirror, what)
+    out = torch.empty((n, C_) + roi, dtype=torch.float32, device=volume.device)
+    a.batch, a.channels, a.cval = B, C_, cval
+    a.size[:], a.roi[:] = size, roi
+    a.stride_b, a.stride_c, a.stride_z, a.stride_y, a.stride_x = sb, sc, sz, sy, 1
+    a.volume, a.windows_out, a.stream = volume.data_ptr(), out.data_ptr(), L.stream_handle(volume)
+    lib.check(lib.dll.segm_window_gather(a), what)
+    return out
+
+
+def window_count(lib: L.SegmLib, weight: torch.Tensor, size, starts) -> torch.Tensor:
+    """weight (*roi) fp32 dense, `starts` the window starts of the three axes (1 .. 64 each, in order) in the padded frame
+    image = max(size, roi) -> the count map (*image) fp32: per voxel the weights of the covering windows, added in the order of the
+    lists' product (z outermost, x fastest) - the bits of the loop `count[slice] += weight`."""
+    what = "window_count"
+    if not isinstance(weight, torch.Tensor) or weight.dim() != 3:
+        raise RuntimeError(f"{what}: a weight map (rz, ry, rx) is required, got {getattr(weight, 'shape', type(weight))}")
+    size, roi, image = _stitch_sides(size, weight.shape, what)
+    _stitch_dense(weight, roi, (torch.float32,), None, f"{what}: weight")
+    starts = [[int(v) for v in axis] for axis in starts]
+    if len(starts) != 3 or any(not 1 <= len(axis) <= L.STITCH_MAX_STARTS for axis in starts):
+        raise RuntimeError(f"{what}: three lists of 1 .. {L.STITCH_MAX_STARTS} window starts are required, got {starts}")
+    a = L.StitchArgs()
+    for d, axis in enumerate(starts):
+        if any(not 0 <= v <= image[d] - roi[d] for v in axis):
+            raise RuntimeError(f"{what}: axis {d}: a start of {axis} leaves the image {image} (roi {roi})")
+        a.n_starts[d] = len(axis)
+        for i, v in enumerate(axis):
+            a.starts[d][i] = v
+    count = torch.empty(image, dtype=torch.float32, device=weight.device)
+    a.batch, a.channels = 1, 1
+    a.size[:], a.roi[:] = size, roi
+    a.weight, a.count, a.stream = weight.data_ptr(), count.data_ptr(), L.stream_handle(weight)
+    lib.check(lib.dll.segm_window_count(a), what)
+    return count
+
+
+def window_blend(lib: L.SegmLib, acc: torch.Tensor, pred: torch.Tensor, weight: torch.Tensor, windows) -> torch.Tensor:
+    """acc (B, Cout, *image) fp32 dense, pred (n, Cout, *roi) dense in fp32 / bf16 / fp16, weight (*roi) fp32, `windows` n tuples
+    (sample, start z, y, x): acc[sample, :, start + i] += fl32(float(pred[n, :, i]) * weight[i]), the windows in their order, every
+    voxel of acc written by one thread (windows of a launch may overlap).  -> acc."""
+    what = "window_blend"
+    if not isinstance(acc, torch.Tensor) or acc.dim() != 5 or not isinstance(pred, torch.Tensor) or pred.dim() != 5:
+        raise RuntimeError(f"{what}: acc (B, Cout, Z, Y, X) and pred (n, Cout, rz, ry, rx) are required, got "
+                           f"{getattr(acc, 'shape', type(acc))} and {getattr(pred, 'shape', type(pred))}")
+    B, C_ = int(acc.shape[0]), int(acc.shape[1])
+    if B < 1 or C_ < 1 or B * C_ > 65535:
+        raise RuntimeError(f"{what}: 1 .. 65535 planes (samples x channels) are required, got {tuple(acc.shape)}")
+    image, roi, _ = _stitch_sides(acc.shape[2:], pred.shape[2:], what)
+    if any(r > s for r, s in zip(roi, image)):
+        raise RuntimeError(f"{what}: the windows {roi} are larger than the accumulator {image}")
+    _stitch_dense(acc, (B, C_) + image, (torch.float32,), None, f"{what}: acc")
+    a = L.StitchArgs()
+    n = _stitch_windows(a, windows, B, C_, image, roi, what)
+    _stitch_dense(pred, (n, C_) + roi, (torch.float32, torch.bfloat16, torch.float16), acc, f"{what}: pred")
+    _stitch_dense(weight, roi, (torch.float32,), acc, f"{what}: weight")
+    a.batch, a.channels, a.dtype = B, C_, L.dtype_code(pred)
+    a.size[:], a.roi[:] = image, roi
+    a.pred, a.weight, a.acc, a.stream = pred.data_ptr(), weight.data_ptr(), acc.data_ptr(), L.stream_handle(acc)
+    lib.check(lib.dll.segm_window_blend(a), what)
+    return acc
+
+
+def window_finish(lib: L.SegmLib, acc: torch.Tensor, count: torch.Tensor, total: torch.Tensor, roi, mirror: int = 0,
+                  pass_index: int = 0, passes: int = 1) -> torch.Tensor:
+    """Closes mirror pass `pass_index` of `passes`.  total (B, Cout, *size) fp32 dense, acc (B, Cout, *image) and count (*image) fp32
+    dense, image = max(size, roi): with p the mirrored position of a voxel in the padded frame, total = acc[p] / count[p] on pass 0
+    and total + acc[p] / count[p] later; the last pass divides by `passes`.  acc is all zero afterwards.  -> total."""
+    what = "window_finish"
+    if not isinstance(total, torch.Tensor) or total.dim() != 5:
+        raise RuntimeError(f"{what}: total (B, Cout, Z, Y, X) is required, got {getattr(total, 'shape', type(total))}")
+    B, C_ = int(total.shape[0]), int(total.shape[1])
+    if B < 1 or C_ < 1 or B * C_ > 65535:
+        raise RuntimeError(f"{what}: 1 .. 65535 planes (samples x channels) are required, got {tuple(total.shape)}")
+    size, roi, image = _stitch_sides(total.shape[2:], roi, what)
+    _stitch_dense(total, (B, C_) + size, (torch.float32,), None, f"{what}: total")
+    _stitch_dense(acc, (B, C_) + image, (torch.float32,), total, f"{what}: acc")
+    _stitch_dense(count, image, (torch.float32,), total, f"{what}: count")
+    if isinstance(passes, bool) or not isinstance(passes, int) or not isinstance(pass_index, int) or passes < 1 \
+            or not 0 <= pass_index < passes:
+        raise RuntimeError(f"{what}: a pass index in [0, passes) is required, got {pass_index!r} of {passes!r}")
+    a = L.StitchArgs()
+    a.mirror = _stitch_mirror(mirror, what)
+    a.batch, a.channels, a.pass_, a.passes = B, C_, pass_index, passes
+    a.size[:], a.roi[:] = size, roi
+    a.acc, a.count, a.total, a.stream = acc.data_ptr(), count.data_ptr(), total.data_ptr(), L.stream_handle(total)
+    lib.check(lib.dll.segm_window_finish(a), what)
+    return total
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -2593,5 +2753,6 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
               "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
               "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "spline_coefs", "affine_spline3", "affine_labels",
-              "zoom_nearest", "gauss_blur", "intensity_stats", "intensity_apply"):
+              "zoom_nearest", "gauss_blur", "intensity_stats", "intensity_apply", "window_gather", "window_count", "window_blend",
+              "window_finish"):
     globals()[_name] = _device_guard(globals()[_name])

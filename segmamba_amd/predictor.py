@@ -15,6 +15,11 @@ full-volume predictions - to host memory and accumulates there (prediction.py:12
 BraTS volume (4 x 240 x 240 x 155 fp32 = 143 MB, 4-class logits the same again) is nothing against 288 GB of HBM: here the
 volume, the weighted accumulator, the weight map and the mirrored copies stay on the device for the whole prediction, the
 eight mirror passes accumulate into one fp32 buffer, and windows go through the network in as large a batch as asked.
+
+Two routes stitch the windows.  `stitch="aten"` (the default) is the chain of ATen calls below.  `stitch="hip"` runs the same
+arithmetic on the kernels of csrc/stitch.hip (`_HipStitch`): the mirror and the centring padding are folded into the window gather
+and into the close of a pass, the count map is built once per prediction, and a window batch is blended in one launch.  The two
+routes are bit-equal; the kernel route is opt-in and never falls back.
 """
 from __future__ import annotations
 
@@ -45,10 +50,8 @@ def dense_patch_starts(image_size: Sequence[int], roi_size: Sequence[int], scan_
     return list(itertools.product(*starts))
 
 
-def importance_map(roi_size: Sequence[int], mode: str = "constant", sigma_scale=0.125, device="cpu",
-                   dtype=torch.float32) -> torch.Tensor:
-    """Window weights (monai/data/utils.py:1117-1138): ones, or a separable gaussian with sigma = sigma_scale * size,
-    clamped from below by max(min, 1e-3)."""
+def _window_weights(roi_size: Sequence[int], mode: str, sigma_scale, device) -> torch.Tensor:
+    """the window weights before the clamp: ones, or the separable gaussian, fp32"""
     if mode == "constant":
         w = torch.ones(tuple(roi_size), device=device, dtype=torch.float32)
     elif mode == "gaussian":
@@ -60,14 +63,115 @@ def importance_map(roi_size: Sequence[int], mode: str = "constant", sigma_scale=
             w = g if w is None else w.unsqueeze(-1) * g[(None,) * i]
     else:
         raise ValueError(f"Unsupported mode: {mode}, available options are ['constant', 'gaussian'].")
+    return w
+
+
+def importance_map(roi_size: Sequence[int], mode: str = "constant", sigma_scale=0.125, device="cpu",
+                   dtype=torch.float32) -> torch.Tensor:
+    """Window weights (monai/data/utils.py:1117-1138): ones, or a separable gaussian with sigma = sigma_scale * size,
+    clamped from below by max(min, 1e-3)."""
+    w = _window_weights(roi_size, mode, sigma_scale, device)
     return torch.clamp(w, min=max(float(w.min()), 1e-3)).to(dtype)
+
+
+def _importance_map_no_sync(roi_size: Sequence[int], mode: str, sigma_scale, device) -> torch.Tensor:
+    """`importance_map` in fp32 with the clamp's bound kept on the device: the same bits (the bound is max(min, fl32(1e-3)) either
+    way, no fp32 value lies between 1e-3 and its fp32 rounding), and nothing is read back to the host"""
+    w = _window_weights(roi_size, mode, sigma_scale, device)
+    return torch.clamp(w, min=torch.clamp(w.min(), min=1e-3))
+
+
+STITCH_ROUTES = ("aten", "hip")
+
+
+def _check_stitch(stitch) -> str:
+    if stitch not in STITCH_ROUTES:
+        raise ValueError(f"Unsupported stitch: {stitch!r}, available options are {list(STITCH_ROUTES)}.")
+    return stitch
+
+
+class _HipStitch:
+    """One prediction on the kernels of csrc/stitch.hip: the geometry of `sliding_window_inference`, the weight map and the count
+    map (once), then per mirror pass `run_pass`: gather a window batch, run the predictor, blend; one finish closes the pass.  The
+    accumulator and the total are shared by the passes.  Nothing is copied to the host and nothing waits for the device."""
+
+    def __init__(self, inputs: torch.Tensor, roi_size, sw_batch_size: int, overlap, mode: str, sigma_scale, padding_mode: str,
+                 cval: float) -> None:
+        from . import lib as L
+        if not isinstance(inputs, torch.Tensor) or inputs.dim() != 5:
+            raise NotImplementedError(f'stitch="hip" takes 3-D volumes (B, C, Z, Y, X), got shape {tuple(getattr(inputs, "shape", ()))}; '
+                                      'use stitch="aten"')
+        if inputs.dtype != torch.float32:
+            raise NotImplementedError(f'stitch="hip" takes float32 volumes, got {inputs.dtype}; use stitch="aten"')
+        if padding_mode != "constant":
+            raise NotImplementedError(f'stitch="hip" pads with a constant only, got padding_mode={padding_mode!r}; use stitch="aten"')
+        if not L.on_device(inputs):
+            raise RuntimeError(f'stitch="hip" runs on the HIP library\'s kernels (csrc/stitch.hip): the volume must live on the GPU, '
+                               f'got a tensor on {inputs.device}; use stitch="aten" on host tensors')
+        if int(sw_batch_size) < 1:
+            raise ValueError(f"sw_batch_size must be at least 1, got {sw_batch_size}.")
+        self.lib = L.get_lib()
+        overlap = _tuple3(overlap, 3)
+        if any(o < 0 or o >= 1 for o in overlap):
+            raise ValueError(f"overlap must be >= 0 and < 1, got {overlap}.")
+        self.batch = int(inputs.shape[0])
+        self.size = tuple(int(v) for v in inputs.shape[2:])
+        self.roi = tuple(int(r) if r and r > 0 else int(s) for r, s in zip(_tuple3(roi_size, 3), self.size))
+        self.image = tuple(max(s, r) for s, r in zip(self.size, self.roi))
+        interval = tuple(r if r == s else max(int(r * (1 - o)), 1) for r, s, o in zip(self.roi, self.image, overlap))
+        starts = dense_patch_starts(self.image, self.roi, interval)
+        self.jobs = [(b,) + tuple(st) for b in range(self.batch) for st in starts]
+        self.sw_batch_size, self.cval = int(sw_batch_size), float(cval)
+        from . import ops_raw
+        self.ops = ops_raw
+        self.weight = _importance_map_no_sync(self.roi, mode, sigma_scale, inputs.device)
+        axis_starts = [sorted(set(st[d] for st in starts)) for d in range(3)]
+        self.count = ops_raw.window_count(self.lib, self.weight, self.size, axis_starts)
+        self.acc: Optional[torch.Tensor] = None
+
+    def run_pass(self, x: torch.Tensor, predictor: Callable[..., torch.Tensor], mirror: int, total: Optional[torch.Tensor],
+                 index: int, passes: int, *args, **kwargs) -> torch.Tensor:
+        """mirror pass `index` of `passes` of the volume x under the flip mask `mirror` -> total (allocated on pass 0)"""
+        from . import lib as L
+        if tuple(x.shape[2:]) != self.size or int(x.shape[0]) != self.batch or x.dtype != torch.float32 or not L.on_device(x):
+            raise RuntimeError(f'stitch="hip": the volume changed between passes: {tuple(x.shape)} {x.dtype} on {x.device}')
+        lib, ops, cap = self.lib, self.ops, L.STITCH_MAX_WINDOWS
+        for j0 in range(0, len(self.jobs), self.sw_batch_size):
+            chunk = self.jobs[j0:j0 + self.sw_batch_size]
+            parts = [ops.window_gather(lib, x, self.roi, chunk[k:k + cap], mirror, self.cval) for k in range(0, len(chunk), cap)]
+            win = parts[0] if len(parts) == 1 else torch.cat(parts)
+            pred = predictor(win, *args, **kwargs)
+            if not isinstance(pred, torch.Tensor) or pred.dim() != 5 or tuple(pred.shape[2:]) != self.roi:
+                raise RuntimeError("sliding_window_inference: the predictor must keep the window's spatial size")
+            if int(pred.shape[0]) != len(chunk):
+                raise RuntimeError(f"sliding_window_inference: the predictor returned {int(pred.shape[0])} windows for {len(chunk)}")
+            if not L.on_device(pred) or pred.device != x.device:
+                raise RuntimeError(f'stitch="hip": the predictor\'s output must stay on {x.device}, got {pred.device}')
+            if pred.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+                raise NotImplementedError(f'stitch="hip" blends float32, bfloat16 or float16 predictions, got {pred.dtype}')
+            if self.acc is None:
+                self.acc = torch.zeros((self.batch, int(pred.shape[1])) + self.image, dtype=torch.float32, device=x.device)
+            elif int(pred.shape[1]) != int(self.acc.shape[1]):
+                raise RuntimeError(f"sliding_window_inference: the predictor returned {int(pred.shape[1])} channels after "
+                                   f"{int(self.acc.shape[1])}")
+            pred = pred.detach().contiguous()
+            for k in range(0, len(chunk), cap):
+                ops.window_blend(lib, self.acc, pred[k:k + cap], self.weight, chunk[k:k + cap])
+        if total is None:
+            total = torch.empty(tuple(self.acc.shape[:2]) + self.size, dtype=torch.float32, device=x.device)
+        return ops.window_finish(lib, self.acc, self.count, total, self.roi, mirror, index, passes)
 
 
 def sliding_window_inference(inputs: torch.Tensor, roi_size, sw_batch_size: int, predictor: Callable[..., torch.Tensor],
                              overlap=0.25, mode: str = "constant", sigma_scale=0.125, padding_mode: str = "constant",
-                             cval: float = 0.0, *args, **kwargs) -> torch.Tensor:
+                             cval: float = 0.0, *args, stitch: str = "aten", **kwargs) -> torch.Tensor:
     """inputs (B, C, *spatial) -> predictor outputs stitched to (B, C_out, *spatial); the reference's blending:
-    sum_w (weight * prediction) / sum_w weight, accumulated in the input's dtype on the input's device."""
+    sum_w (weight * prediction) / sum_w weight, accumulated in the input's dtype on the input's device.
+    `stitch="hip"` (keyword only): the same result, bit for bit, on the kernels of csrc/stitch.hip - 3-D float32 volumes on the
+    GPU with constant padding; anything else raises."""
+    if _check_stitch(stitch) == "hip":
+        return _HipStitch(inputs, roi_size, sw_batch_size, overlap, mode, sigma_scale, padding_mode, cval).run_pass(
+            inputs, predictor, 0, None, 0, 1, *args, **kwargs)
     nd = inputs.dim() - 2
     overlap = _tuple3(overlap, nd)
     if any(o < 0 or o >= 1 for o in overlap):
@@ -116,13 +220,19 @@ class SlidingWindowInferer:
     """Constructor-compatible with the object the reference builds (4_predict.py:55-59, 3_train.py:35-37)."""
 
     def __init__(self, roi_size, sw_batch_size: int = 1, overlap=0.25, mode: str = "constant", sigma_scale=0.125,
-                 padding_mode: str = "constant", cval: float = 0.0, progress: bool = False, **unused) -> None:
+                 padding_mode: str = "constant", cval: float = 0.0, progress: bool = False, stitch: str = "aten", **unused) -> None:
         self.roi_size, self.sw_batch_size, self.overlap = roi_size, sw_batch_size, overlap
         self.mode, self.sigma_scale, self.padding_mode, self.cval = mode, sigma_scale, padding_mode, cval
+        self.stitch = _check_stitch(stitch)
 
     def __call__(self, inputs: torch.Tensor, network: Callable[..., torch.Tensor], *args, **kwargs) -> torch.Tensor:
         return sliding_window_inference(inputs, self.roi_size, self.sw_batch_size, network, self.overlap, self.mode,
-                                        self.sigma_scale, self.padding_mode, self.cval, *args, **kwargs)
+                                        self.sigma_scale, self.padding_mode, self.cval, *args, stitch=self.stitch, **kwargs)
+
+    def stitcher(self, inputs: torch.Tensor) -> _HipStitch:
+        """the kernel route's state for one prediction of `inputs` (stitch="hip")"""
+        return _HipStitch(inputs, self.roi_size, self.sw_batch_size, self.overlap, self.mode, self.sigma_scale, self.padding_mode,
+                          self.cval)
 
 
 class Predictor:
@@ -153,6 +263,12 @@ class Predictor:
         with torch.no_grad(), torch.autocast("cuda", dtype=self.autocast_dtype,
                                              enabled=device.type == "cuda" and self.autocast_dtype != torch.float32):
             total = None
+            if isinstance(self.window_infer, SlidingWindowInferer) and self.window_infer.stitch == "hip":
+                # one accumulator, one count map and one total for all passes; the mirror is an index in gather and finish
+                state = self.window_infer.stitcher(x)
+                for i, c in enumerate(combos):
+                    total = state.run_pass(x, model, sum(1 << a for a in c), total, i, len(combos), **kwargs)
+                return total
             for c in combos:
                 dims = tuple(a + 2 for a in c)
                 xin = torch.flip(x, dims) if dims else x
