@@ -947,7 +947,8 @@ int segm_planes_bbox(const segm_planes_bbox_args* args);
  * predict_noncrop_probability (:64-108) by ONE launch, and large_connected_domain (:17-27: skimage.measure.label at connectivity 1,
  * keep the largest, scipy.ndimage.binary_fill_holes) by connected components on the device.
  * ------------------------------------------------------------------------------------------------ */
-#define SEGM_RESAMPLE_MAX_CLASSES 8
+#define SEGM_RESAMPLE_MAX_CLASSES 8              /* the default bound of the Python wrapper (a BraTS-sized class count) */
+#define SEGM_RESAMPLE_CLASS_LIMIT 32             /* what segm_resample_argmax accepts: the kernel loops over the classes */
 #define SEGM_CCL_MAX_VOXELS 2147483647LL         /* depth * height * width < 2^31: labels are int32 linear indices */
 
 /* Logits (classes, in_depth, in_height, in_width) -> uint8 label volume (out_depth, out_height, out_width).  For every voxel of the
@@ -958,7 +959,9 @@ int segm_planes_bbox(const segm_planes_bbox_args* args);
  * the logits' size the weights are exactly 0 / 1 and the result is the plain argmax.
  * regions (optional, else NULL): a second (out_depth, out_height, out_width) uint8 volume = table[label], the region bit planes that
  * the evaluation entries take; `table` (256 bytes, device memory) is required with it.
- * dtype SEGM_F32 / SEGM_F16 / SEGM_BF16; element strides for class, z and y, unit stride along x; `logits` aligned to its element size. */
+ * dtype SEGM_F32 / SEGM_F16 / SEGM_BF16; element strides for class, z and y, unit stride along x; `logits` aligned to its element size.
+ * 1 .. SEGM_RESAMPLE_CLASS_LIMIT classes (the reference's CT example takes the argmax over 10:
+ * light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:87-109). */
 typedef struct segm_resample_argmax_args {
     int32_t classes, dtype;
     int32_t in_depth, in_height, in_width;
@@ -1023,6 +1026,46 @@ typedef struct segm_ccl_select_args {
 } segm_ccl_select_args;
 size_t segm_ccl_select_workspace_bytes(int64_t voxels);
 int segm_ccl_select(const segm_ccl_select_args* args);
+
+/* Labelled connected components (additive to ABI 10; csrc/ccl_labels.hip): every class of a label map in ONE pass.  What the
+ * reference's CT example needs per organ (4_predict_diffunet.py:97-109 writes `labels == i` per organ; prediction.py:17-27
+ * `large_connected_domain` keeps the largest component) and nnU-Net's "keep the largest component of every class".
+ * Two voxels belong to one component when a path of face neighbours (connectivity 1) with the SAME NON-ZERO label joins them.
+ *   roots[i] = -1 where the label is 0, otherwise the SMALLEST linear index of the voxel's component
+ * - the definition of segm_ccl_roots, so roots[labels == c] equals segm_ccl_roots of the mask `labels == c` on those voxels, the
+ * result depends on no order and two calls are bit-equal.  Three launches, no readback; workspace: one int32 per voxel.
+ * segm_ccl_sizes takes these roots unchanged. */
+typedef struct segm_ccl_label_roots_args {
+    int32_t depth, height, width, reserved;
+    const uint8_t* labels;         /* (depth, height, width) */
+    int32_t* roots;                /* (depth, height, width) */
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_ccl_label_roots_args;
+size_t segm_ccl_label_roots_workspace_bytes(int64_t voxels);
+int segm_ccl_label_roots(const segm_ccl_label_roots_args* args);
+
+/* Selection per label from the label volume, its roots and their sizes.  mode SEGM_CCL_LARGEST: a voxel keeps its label iff its
+ * component is the largest OF ITS LABEL (equal sizes: the root that comes LAST in memory); SEGM_CCL_MIN_SIZE: iff its component has
+ * at least min_size voxels; otherwise it becomes 0.  SEGM_CCL_FILL is not a mode here.
+ * apply (optional, 256 bytes, device memory): apply[l] == 0 passes label l through untouched; NULL selects on every label.
+ * info (256 x 3 int64 in device memory, OVERWRITTEN): per label the number of components, the winner's root (-1: label absent) and
+ * the winner's voxel count.  The winner is an integer maximum over (size << 32) | root: per workgroup in LDS, then one 64-bit atomic
+ * max per label and workgroup into the workspace - no floating point, two calls are bit-equal.  One memset and two launches. */
+typedef struct segm_ccl_label_select_args {
+    int32_t depth, height, width;
+    int32_t mode, min_size, reserved;
+    const uint8_t* labels;
+    const int32_t* roots;
+    const int32_t* sizes;
+    const uint8_t* apply;          /* optional */
+    uint8_t* out;                  /* (depth, height, width) */
+    int64_t* info;                 /* [256][3] */
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_ccl_label_select_args;
+size_t segm_ccl_label_select_workspace_bytes(int64_t voxels);
+int segm_ccl_label_select(const segm_ccl_label_select_args* args);
 
 /* ------------------------------------------------------------------------------------------------
  * Preparing a case on the device (additive to ABI 10; csrc/preprocess.hip).

@@ -32,27 +32,9 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "segm_device.h"
+#include "ccl_common.h"
 
 namespace segm {
-
-#ifdef SEGM_EMU
-constexpr int kScopeWorkgroup = 0, kScopeAgent = 1;
-template <int S> static inline int32_t lab_load(int32_t* p) { return __atomic_load_n(p, __ATOMIC_RELAXED); }
-template <int S> static inline int32_t lab_min(int32_t* p, int32_t v) { return __atomic_fetch_min(p, v, __ATOMIC_RELAXED); }
-template <int S> static inline int32_t cnt_add(int32_t* p, int32_t v) { return __atomic_fetch_add(p, v, __ATOMIC_RELAXED); }
-#else
-constexpr int kScopeWorkgroup = __HIP_MEMORY_SCOPE_WORKGROUP, kScopeAgent = __HIP_MEMORY_SCOPE_AGENT;
-template <int S> __device__ __forceinline__ int32_t lab_load(int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, S); }
-template <int S> __device__ __forceinline__ int32_t lab_min(int32_t* p, int32_t v) { return __hip_atomic_fetch_min(p, v, __ATOMIC_RELAXED, S); }
-template <int S> __device__ __forceinline__ int32_t cnt_add(int32_t* p, int32_t v) { return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, S); }
-#endif
-
-constexpr int kTX = 64, kTY = 4, kTZ = 4;           // the tile: a wave per z, four rows along x per wave
-constexpr int kTileRows = kTY * kTZ;
-constexpr int kTileVox = kTX * kTileRows;
-constexpr int kPostVox = 16;                        // voxels per thread of the counting passes
-constexpr int kPostChunk = kBlock * kPostVox;
 
 // ---- logits -> labels ---------------------------------------------------------------------------------------------------------------
 struct ResDev {
@@ -183,29 +165,6 @@ struct CclDev {
 __device__ __forceinline__ bool ccl_inside(uint32_t v, int bit, int invert) {
     const int in = bit >= 0 ? (int)((v >> bit) & 1u) : (int)(v != 0u);
     return in != invert;
-}
-
-// the end of a's chain: labels never grow and a root names itself
-template <int S> __device__ __forceinline__ int32_t lab_find(int32_t* L, int32_t a) {
-    for (;;) {
-        const int32_t p = lab_load<S>(L + a);
-        if (p == a) return a;
-        a = p;
-    }
-}
-
-// joins the components of a and b: the larger root is hung below the smaller one.  When another thread got there first (`old` is not
-// the root we saw) the link it made is kept by carrying on with `old` and b.
-template <int S> __device__ __forceinline__ void lab_union(int32_t* L, int32_t a, int32_t b) {
-    for (;;) {
-        a = lab_find<S>(L, a);
-        b = lab_find<S>(L, b);
-        if (a == b) return;
-        if (a < b) { const int32_t t = a; a = b; b = t; }
-        const int32_t old = lab_min<S>(L + a, b);
-        if (old == a) return;
-        a = old;
-    }
 }
 
 __global__ void __launch_bounds__(kBlock) ccl_tile_kernel(CclDev P) {
@@ -400,14 +359,6 @@ __global__ void __launch_bounds__(kBlock) ccl_select_kernel(SelDev P) {
     P.out[i] = on ? 1 : 0;
 }
 
-static inline bool ccl_volume_ok(int64_t d, int64_t h, int64_t w) {
-    if (d <= 0 || h <= 0 || w <= 0) return false;
-    if (d > SEGM_CCL_MAX_VOXELS || h > SEGM_CCL_MAX_VOXELS || w > SEGM_CCL_MAX_VOXELS) return false;
-    if (d * h > SEGM_CCL_MAX_VOXELS) return false;
-    return d * h * w <= SEGM_CCL_MAX_VOXELS;
-}
-static inline int64_t post_blocks(int64_t nvox) { return (nvox + kPostChunk - 1) / kPostChunk; }
-
 }  // namespace segm
 
 using namespace segm;
@@ -415,7 +366,7 @@ using namespace segm;
 extern "C" int segm_resample_argmax(const segm_resample_argmax_args* a) {
     if (!a) return SEGM_E_NULL;
     if (!a->logits || !a->labels || (a->regions && !a->table)) return SEGM_E_NULL;
-    if (a->classes < 1 || a->classes > SEGM_RESAMPLE_MAX_CLASSES) return SEGM_E_SHAPE;
+    if (a->classes < 1 || a->classes > SEGM_RESAMPLE_CLASS_LIMIT) return SEGM_E_SHAPE;
     if (a->in_depth <= 0 || a->in_height <= 0 || a->in_width <= 0) return SEGM_E_SHAPE;
     if (!ccl_volume_ok(a->out_depth, a->out_height, a->out_width)) return SEGM_E_SHAPE;
     if (a->box_depth <= 0 || a->box_height <= 0 || a->box_width <= 0 || a->box_z < 0 || a->box_y < 0 || a->box_x < 0) return SEGM_E_SHAPE;

@@ -300,6 +300,7 @@ EXPORTS = (
     "segm_edt_sq_long", "segm_edt_sq_long_workspace_bytes", "segm_planes_bbox",
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
+    "segm_ccl_label_roots", "segm_ccl_label_roots_workspace_bytes", "segm_ccl_label_select", "segm_ccl_label_select_workspace_bytes",
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
     "segm_crop_clip_normalize", "segm_fg_workspace_bytes", "segm_fg_count", "segm_fg_order_stats", "segm_fg_gather",
     "segm_cross_entropy_map", "segm_cross_entropy_map_bwd", "segm_topk_select", "segm_topk_select_workspace_bytes",
@@ -374,6 +375,7 @@ class BorderDistancesArgs(C.Structure):
 
 RESAMPLE_MAX_CLASSES, CCL_MAX_VOXELS = 8, 2 ** 31 - 1                         # SEGM_RESAMPLE_MAX_CLASSES / SEGM_CCL_MAX_VOXELS
 CCL_LARGEST, CCL_MIN_SIZE, CCL_FILL = 0, 1, 2                                  # enum segm_ccl_select_mode
+RESAMPLE_CLASS_LIMIT = 32                                                      # SEGM_RESAMPLE_CLASS_LIMIT: what the C entry accepts
 
 
 class ResampleArgmaxArgs(C.Structure):
@@ -403,6 +405,19 @@ class CclSelectArgs(C.Structure):
                 ("mode", C.c_int32), ("min_size", C.c_int32), ("reserved", C.c_int32),
                 ("roots", C.c_void_p), ("sizes", C.c_void_p), ("touches", C.c_void_p), ("out", C.c_void_p), ("info", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class CclLabelRootsArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("labels", C.c_void_p), ("roots", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class CclLabelSelectArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("mode", C.c_int32), ("min_size", C.c_int32), ("reserved", C.c_int32),
+                ("labels", C.c_void_p), ("roots", C.c_void_p), ("sizes", C.c_void_p), ("apply", C.c_void_p), ("out", C.c_void_p),
+                ("info", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
 PREP_MAX_CHANNELS, PREP_COUNT_BINS = 8, 260                                    # SEGM_PREP_MAX_CHANNELS / SEGM_PREP_COUNT_BINS
@@ -677,6 +692,10 @@ class SegmLib:
         sig("segm_ccl_sizes", [C.POINTER(CclSizesArgs)], C.c_int)
         sig("segm_ccl_select", [C.POINTER(CclSelectArgs)], C.c_int)
         sig("segm_ccl_select_workspace_bytes", [C.c_int64], C.c_size_t)
+        sig("segm_ccl_label_roots", [C.POINTER(CclLabelRootsArgs)], C.c_int)
+        sig("segm_ccl_label_roots_workspace_bytes", [C.c_int64], C.c_size_t)
+        sig("segm_ccl_label_select", [C.POINTER(CclLabelSelectArgs)], C.c_int)
+        sig("segm_ccl_label_select_workspace_bytes", [C.c_int64], C.c_size_t)
         sig("segm_nonzero_mask_bbox", [C.POINTER(NonzeroMaskBboxArgs)], C.c_int)
         sig("segm_crop_stats", [C.POINTER(CropArgs)], C.c_int)
         sig("segm_crop_stats_workspace_bytes", [C.c_int32] * 4, C.c_size_t)

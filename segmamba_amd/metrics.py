@@ -70,6 +70,12 @@ def _table(regions, device) -> torch.Tensor:
     return _tables[key]
 
 
+def _groups(regions):
+    """the regions in groups of at most L.METRICS_MAX_REGIONS: the kernels carry 8 region planes per call"""
+    regions = list(regions)
+    return [regions[i:i + L.METRICS_MAX_REGIONS] for i in range(0, len(regions), L.METRICS_MAX_REGIONS)]
+
+
 def _to_device(x) -> torch.Tensor:
     t = torch.from_numpy(np.ascontiguousarray(x)) if isinstance(x, np.ndarray) else x
     if not isinstance(t, torch.Tensor):
@@ -115,6 +121,8 @@ def _dice(p: int, g: int, both: int) -> float:
 def region_masks(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS) -> torch.Tensor:
     """`convert_labels` of the reference: (n_regions, *labels.shape) fp32 masks, region r = labels in regions[r]"""
     t = _labels(labels)
+    if len(regions) > L.METRICS_MAX_REGIONS:                              # any number of regions: eight at a time
+        return torch.cat([region_masks(t, g) for g in _groups(regions)])
     bits = _table(regions, t.device)[t.long()]
     return torch.stack([(bits >> r) & 1 for r in range(len(regions))]).float()
 
@@ -251,10 +259,17 @@ def hd(result, reference, voxelspacing: Optional[Sequence[float]] = None) -> flo
 
 
 def case_metrics(pred_labels, gt_labels, voxelspacing: Optional[Sequence[float]] = (1, 1, 1),
-                 regions: Sequence[Sequence[int]] = BRATS_REGIONS) -> np.ndarray:
+                 regions: Sequence[Sequence[int]] = BRATS_REGIONS, max_regions: Optional[int] = L.METRICS_MAX_REGIONS) -> np.ndarray:
     """`each_cases_metric` of 5_compute_metrics.py on label volumes: (n_regions, 2) = [dice, hd95] per region, with the reference's rule
-    for empty masks (`cal_metric`, :24-30): [0.0, 50] unless both the prediction and the ground truth of the region are non-empty."""
+    for empty masks (`cal_metric`, :24-30): [0.0, 50] unless both the prediction and the ground truth of the region are non-empty.
+    `max_regions` bounds the number of regions a call accepts (8 by default: what one kernel call carries, and what this function
+    always refused beyond); `max_regions=None` takes any number, e.g. one region per organ, and runs them in groups of 8 through the
+    same kernels (two readbacks per group), concatenated."""
     pred, gt = _pair(pred_labels, gt_labels, _labels, "case_metrics")
+    if max_regions is not None and len(regions) > int(max_regions):
+        raise RuntimeError(f"case_metrics: at most {int(max_regions)} regions per call (max_regions=None lifts the bound), got {len(regions)}")
+    if len(regions) > L.METRICS_MAX_REGIONS:                              # eight at a time, concatenated
+        return np.concatenate([case_metrics(pred, gt, voxelspacing, g) for g in _groups(regions)])
     p = _Pass(pred, gt, regions)
     out = np.zeros((len(regions), 2), dtype=np.float64)
     out[:, 1] = 50.0
@@ -272,6 +287,8 @@ def validation_dice(pred_labels, gt_labels, regions: Sequence[Sequence[int]] = B
         raise RuntimeError(f"validation_dice: two label tensors of one shape (..., D, H, W) are required, got {tuple(pred.shape)} and {tuple(gt.shape)}")
     if gt.device != pred.device:
         gt = gt.to(pred.device)
+    if len(regions) > L.METRICS_MAX_REGIONS:
+        return np.concatenate([validation_dice(pred, gt, g) for g in _groups(regions)])
     shape = (-1,) + tuple(pred.shape[-2:])
     _, counts = ops_raw.seg_regions(L.get_lib(), pred.reshape(shape), gt.reshape(shape), _table(regions, pred.device))
     c = counts[:, :len(regions)].tolist()
@@ -282,13 +299,14 @@ def validation_dice(pred_labels, gt_labels, regions: Sequence[Sequence[int]] = B
     return out
 
 
-def evaluate(cases: Iterable, regions: Sequence[Sequence[int]] = BRATS_REGIONS):
+def evaluate(cases: Iterable, regions: Sequence[Sequence[int]] = BRATS_REGIONS, max_regions: Optional[int] = L.METRICS_MAX_REGIONS):
     """cases: an iterable of (pred_labels, gt_labels) or (pred_labels, gt_labels, voxelspacing).  -> (results (n, n_regions, 2), their
-    mean over the cases, their standard deviation): what 5_compute_metrics.py:76-84 saves and prints."""
+    mean over the cases, their standard deviation): what 5_compute_metrics.py:76-84 saves and prints.  `max_regions`: see
+    `case_metrics`."""
     rows = []
     for case in cases:
         spacing = case[2] if len(case) > 2 else (1, 1, 1)
-        rows.append(case_metrics(case[0], case[1], spacing, regions))
+        rows.append(case_metrics(case[0], case[1], spacing, regions, max_regions))
     results = np.stack(rows) if rows else np.zeros((0, len(regions), 2))
     if not rows:
         return results, np.full((len(regions), 2), np.nan), np.full((len(regions), 2), np.nan)

@@ -1888,8 +1888,9 @@ def _ccl_volume(t: torch.Tensor, what: str, dtype=torch.uint8) -> None:
 
 
 def resample_argmax(lib: L.SegmLib, logits: torch.Tensor, out_shape=None, box_start=(0, 0, 0), box_shape=None, table=None,
-                    out: torch.Tensor = None):
-    """logits (C, d, h, w) fp32 / bf16 / fp16 with a unit stride along w, C <= 8.  -> uint8 labels of shape `out_shape`: inside the box
+                    out: torch.Tensor = None, max_classes: int = L.RESAMPLE_MAX_CLASSES):
+    """logits (C, d, h, w) fp32 / bf16 / fp16 with a unit stride along w, C <= `max_classes` (8 unless the caller raises it, at most
+    L.RESAMPLE_CLASS_LIMIT).  -> uint8 labels of shape `out_shape`: inside the box
     `box_start` + `box_shape` the arg-max over the classes of the logits resampled (trilinear, align_corners False) to the box's
     shape, 0 outside.  Defaults: the box has the logits' shape and fills the output.  With `table` (256 uint8, device) also the
     region bit planes table[label]: -> (labels, regions)."""
@@ -1897,8 +1898,11 @@ def resample_argmax(lib: L.SegmLib, logits: torch.Tensor, out_shape=None, box_st
         raise RuntimeError(f"resample_argmax: logits (C, d, h, w) required, got {getattr(logits, 'shape', type(logits))}")
     dtype = L.dtype_code(logits)
     C_, d, h, w = logits.shape
-    if not 1 <= C_ <= L.RESAMPLE_MAX_CLASSES or min(d, h, w) < 1:
-        raise RuntimeError(f"resample_argmax: 1 .. {L.RESAMPLE_MAX_CLASSES} classes and a non-empty volume, got {tuple(logits.shape)}")
+    max_classes = int(max_classes)
+    if not 1 <= max_classes <= L.RESAMPLE_CLASS_LIMIT:
+        raise RuntimeError(f"resample_argmax: max_classes must lie in 1 .. {L.RESAMPLE_CLASS_LIMIT}, got {max_classes}")
+    if not 1 <= C_ <= max_classes or min(d, h, w) < 1:
+        raise RuntimeError(f"resample_argmax: 1 .. {max_classes} classes and a non-empty volume, got {tuple(logits.shape)}")
     sc, sz, sy, sx = logits.stride()
     if w > 1 and sx != 1:
         raise RuntimeError("resample_argmax: logits need a unit stride along the last dimension")
@@ -2000,6 +2004,57 @@ def ccl_select(lib: L.SegmLib, roots: torch.Tensor, sizes: torch.Tensor, mode: i
     a.touches = None if touches is None else touches.data_ptr()
     a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), nbytes, L.stream_handle(roots)
     lib.check(lib.dll.segm_ccl_select(a), "ccl_select")
+    return out, info
+
+
+def ccl_label_roots(lib: L.SegmLib, labels: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """Connected components at connectivity 1 of every class of a label volume in one pass: two voxels are joined by face neighbours
+    of the same non-zero label.  labels (D, H, W) uint8.  -> int32 (D, H, W): -1 where the label is 0, else the smallest linear index
+    of the voxel's component (on `labels == c` what `ccl_roots(labels == c)` gives)."""
+    _ccl_volume(labels, "ccl_label_roots: labels")
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
+    else:
+        _same_volume(out, "ccl_label_roots: out", torch.int32, labels.shape, labels.device)
+    nbytes = lib.dll.segm_ccl_label_roots_workspace_bytes(labels.numel())
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
+    a = L.CclLabelRootsArgs()
+    a.depth, a.height, a.width = labels.shape
+    a.labels, a.roots, a.workspace, a.workspace_bytes, a.stream = labels.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(labels)
+    lib.check(lib.dll.segm_ccl_label_roots(a), "ccl_label_roots")
+    return out
+
+
+def ccl_label_select(lib: L.SegmLib, labels: torch.Tensor, roots: torch.Tensor, sizes: torch.Tensor, mode: int, min_size: int = 0,
+                     apply: torch.Tensor = None, out: torch.Tensor = None):
+    """-> (labels uint8 (D, H, W), info int64 (256, 3) on the device = per label [components, root of the largest or -1, its voxel
+    count]).  mode L.CCL_LARGEST: a voxel keeps its label iff its component is the largest of its label (equal counts: the root that
+    comes last); L.CCL_MIN_SIZE: iff its component has at least `min_size` voxels.  `apply` (256 uint8 on the device): labels whose
+    entry is 0 pass through untouched; None selects on every label."""
+    _ccl_volume(labels, "ccl_label_select: labels")
+    _same_volume(roots, "ccl_label_select: roots", torch.int32, labels.shape, labels.device)
+    _same_volume(sizes, "ccl_label_select: sizes", torch.int32, labels.shape, labels.device)
+    if mode not in (L.CCL_LARGEST, L.CCL_MIN_SIZE):
+        raise RuntimeError(f"ccl_label_select: mode must be CCL_LARGEST or CCL_MIN_SIZE, got {mode}")
+    min_size = int(min_size)
+    if not 0 <= min_size <= L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"ccl_label_select: min_size must lie in [0, 2^31 - 1], got {min_size}")
+    if apply is not None:
+        _same_volume(apply, "ccl_label_select: apply", torch.uint8, (256,), labels.device)
+    if out is None:
+        out = torch.empty(labels.shape, dtype=torch.uint8, device=labels.device)
+    else:
+        _same_volume(out, "ccl_label_select: out", torch.uint8, labels.shape, labels.device)
+    info = torch.empty((256, 3), dtype=torch.int64, device=labels.device)
+    nbytes = lib.dll.segm_ccl_label_select_workspace_bytes(labels.numel())
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=labels.device)
+    a = L.CclLabelSelectArgs()
+    a.depth, a.height, a.width = labels.shape
+    a.mode, a.min_size = mode, min_size
+    a.labels, a.roots, a.sizes, a.out, a.info = labels.data_ptr(), roots.data_ptr(), sizes.data_ptr(), out.data_ptr(), info.data_ptr()
+    a.apply = None if apply is None else apply.data_ptr()
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), nbytes, L.stream_handle(labels)
+    lib.check(lib.dll.segm_ccl_label_select(a), "ccl_label_select")
     return out, info
 
 

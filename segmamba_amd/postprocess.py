@@ -13,6 +13,10 @@ Where this deliberately differs from the reference:
     `np.argsort(volume)[-1]`, which numpy leaves undefined for ties;
   * the resampled logits are compared in fp32 (the CPU branch of `predict_raw_probability`; its GPU branch rounds them to fp16 first).
 `postprocess_labels` (per region of a label map) is this project's addition: the reference applies its function to one binary mask.
+
+Multi-organ label maps (the reference's CT example, light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:87-109: the
+argmax over 10 classes, one file per organ): `labels_from_logits` takes up to 32 classes, and `keep_largest_per_class` keeps the
+largest component of every class from ONE labelled connected-components pass (csrc/ccl_labels.hip) instead of one pass per class.
 """
 from __future__ import annotations
 
@@ -117,13 +121,14 @@ def labels_from_logits(logits, properties: Optional[dict] = None, regions: Optio
         t = t.contiguous()
     table = None if regions is None else _table(regions, t.device)
     if properties is None:
-        return ops_raw.resample_argmax(L.get_lib(), t, table=table)
+        return ops_raw.resample_argmax(L.get_lib(), t, table=table, max_classes=L.RESAMPLE_CLASS_LIMIT)
     box_shape = _ints(properties["shape_after_cropping_before_resample"], 3, "shape_after_cropping_before_resample")
     out_shape = _ints(properties["shape_before_cropping"], 3, "shape_before_cropping")
     bbox = [_ints(bb, 2, "bbox_used_for_cropping") for bb in list(properties["bbox_used_for_cropping"])[:3]]
     if len(bbox) != 3 or any(b1 - b0 != n for (b0, b1), n in zip(bbox, box_shape)):
         raise RuntimeError(f"labels_from_logits: bbox_used_for_cropping {bbox} does not have the shape {box_shape}")
-    return ops_raw.resample_argmax(L.get_lib(), t, out_shape, [b0 for b0, _ in bbox], box_shape, table=table)
+    return ops_raw.resample_argmax(L.get_lib(), t, out_shape, [b0 for b0, _ in bbox], box_shape, table=table,
+                                   max_classes=L.RESAMPLE_CLASS_LIMIT)
 
 
 def postprocess_labels(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS, keep="largest", fill_holes: bool = True) -> torch.Tensor:
@@ -143,3 +148,70 @@ def postprocess_labels(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS,
         inside = ((bits >> r) & 1).bool()
         out[inside & (kept == 0)] = 0
     return out
+
+
+# ---- every class of a label map in one pass (csrc/ccl_labels.hip) ----------------------------------------------------------------------
+def _label_volume(x, what: str) -> torch.Tensor:
+    """uint8, contiguous, (D, H, W), on the device; integer label maps of other types are converted"""
+    t = _to_device(x)
+    if t.dim() != 3:
+        raise RuntimeError(f"{what}: a (D, H, W) label volume is required, got shape {tuple(t.shape)}")
+    if t.numel() == 0 or t.numel() > L.CCL_MAX_VOXELS:
+        raise RuntimeError(f"{what}: between 1 and 2^31 - 1 voxels, got shape {tuple(t.shape)}")
+    if t.dtype != torch.uint8:
+        if t.dtype.is_floating_point or t.dtype == torch.bool:
+            raise RuntimeError(f"{what}: integer labels 0 .. 255 are required, got {t.dtype}")
+        t = t.to(torch.uint8)
+    return t.contiguous()
+
+
+def label_component_roots(labels) -> torch.Tensor:
+    """int32 (D, H, W): -1 where the label is 0, otherwise the smallest linear index of the voxel's component; a component is a set
+    of voxels of ONE non-zero label joined by face neighbours.  On `labels == c` this is `component_roots(labels == c)`."""
+    return ops_raw.ccl_label_roots(L.get_lib(), _label_volume(labels, "label_component_roots"))
+
+
+def _label_select(lib, t: torch.Tensor, keep, apply=None):
+    roots = ops_raw.ccl_label_roots(lib, t)
+    sizes, _ = ops_raw.ccl_sizes(lib, roots)
+    if keep == "largest":
+        return ops_raw.ccl_label_select(lib, t, roots, sizes, L.CCL_LARGEST, apply=apply)
+    return ops_raw.ccl_label_select(lib, t, roots, sizes, L.CCL_MIN_SIZE, min_size=int(keep), apply=apply)
+
+
+def keep_largest_per_class(labels, classes: Optional[Sequence[int]] = None, keep="largest", fill_holes: bool = False) -> torch.Tensor:
+    """nnU-Net's per-class post-processing / the reference's `large_connected_domain` per organ, for a whole label map: every voxel
+    whose component is not the largest of its label becomes 0 (`keep` = a voxel count: not of at least that many voxels).  Equal
+    sizes: the component that comes last in memory order.  `classes` = None selects on every non-zero label, otherwise on the listed
+    ones only and the others pass through.  One labelled pass whatever the number of classes; nothing is read back.
+    With `fill_holes` every selected class present, in ascending order, then has its holes filled (`binary_fill_holes` of its mask);
+    only voxels that are 0 at that moment receive the label.  This reads the per-label summary back once when `classes` is None.
+    -> uint8 labels."""
+    t = _label_volume(labels, "keep_largest_per_class")
+    lib = L.get_lib()
+    apply = None
+    if classes is not None:
+        classes = sorted({int(c) for c in classes})
+        if any(not 1 <= c <= 255 for c in classes):
+            raise RuntimeError(f"keep_largest_per_class: classes must lie in 1 .. 255, got {classes}")
+        table = torch.zeros(256, dtype=torch.uint8)
+        table[classes] = 1
+        apply = table.to(t.device)
+    out, info = _label_select(lib, t, keep, apply)
+    if fill_holes:
+        present = classes
+        if present is None:
+            counts = info[:, 0].tolist()                                  # one readback: which labels there are
+            present = [c for c in range(1, 256) if counts[c]]
+        for c in present:
+            filled = _fill(lib, (out == c).to(torch.uint8))
+            out[(out == 0) & (filled != 0)] = c
+    return out
+
+
+def class_component_summary(labels) -> dict:
+    """{label: (number of components, voxels of the largest)} for every label present: one labelled pass, one readback of 256 x 3
+    integers"""
+    t = _label_volume(labels, "class_component_summary")
+    info = _label_select(L.get_lib(), t, "largest")[1].tolist()
+    return {c: (int(info[c][0]), int(info[c][2])) for c in range(1, 256) if info[c][0]}

@@ -343,3 +343,42 @@ class Predictor:
         nifti.write_nifti(path, out, spacing)
         print(f"{path} is saved successfully")
         return path
+
+    def save_organs_to_nii(self, labels, raw_spacing, save_dir, names: Sequence[str], postprocess: bool = False) -> List[str]:
+        """One file per organ of a multi-class label map: `<save_dir>/<names[i - 1]>.nii.gz` holds `labels == i` for i = 1 .. len(names)
+        (the loop of the reference's light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:97-109).  `labels`: a (D, H, W)
+        label volume, device tensor, host tensor or numpy array.  With `postprocess` each organ is `binary_fill_holes` of its largest
+        component (`large_connected_domain` per organ); the largest components of all organs come from ONE labelled pass on the device
+        (segmamba_amd.postprocess.keep_largest_per_class).  One copy to the host: the uint8 label volume, or with `postprocess` the
+        organs' filled masks packed eight to a byte (filled holes of different organs may overlap).  -> the paths written."""
+        import os
+
+        from . import nifti
+        from . import postprocess as post
+        names = [str(n) for n in names]
+        if not 1 <= len(names) <= 255 or len(set(names)) != len(names):
+            raise RuntimeError(f"save_organs_to_nii: between 1 and 255 distinct organ names are required, got {names}")
+        shape = tuple(labels.shape)
+        if len(shape) == 4 and shape[0] == 1:
+            labels = labels[0]
+        elif len(shape) != 3:
+            raise RuntimeError(f"save_organs_to_nii: a (D, H, W) label volume (or (1, D, H, W)) is required, got shape {shape}")
+        n = len(names)
+        if postprocess:
+            kept = post.keep_largest_per_class(labels, classes=range(1, n + 1))
+            packed = torch.zeros(((n + 7) // 8,) + tuple(kept.shape), dtype=torch.uint8, device=kept.device)
+            for i in range(n):
+                packed[i // 8] |= post.binary_fill_holes(kept == i + 1) << (i % 8)
+            host = packed.cpu().numpy()                                   # the one copy to the host
+            organs = [((host[i // 8] >> (i % 8)) & 1).astype(np.uint8) for i in range(n)]
+        else:
+            host = labels.to(torch.uint8).cpu().numpy() if isinstance(labels, torch.Tensor) else np.asarray(labels).astype(np.uint8)
+            organs = [(host == i + 1).astype(np.uint8) for i in range(n)]
+        spacing = [float(v.item()) if isinstance(v, torch.Tensor) else float(v) for v in list(raw_spacing)[:3]]
+        os.makedirs(save_dir, exist_ok=True)
+        paths = []
+        for name, organ in zip(names, organs):
+            paths.append(os.path.join(save_dir, f"{name}.nii.gz"))
+            nifti.write_nifti(paths[-1], organ, spacing)
+        print(f"{len(paths)} organ files are saved to {save_dir}")
+        return paths

@@ -1,7 +1,9 @@
 """Dice and HD95 per BraTS region (TC / WT / ET) of predicted label volumes against ground truth, on the device: the command-line
 form of the reference's 5_compute_metrics.py.
 
-    python tools/compute_metrics.py --pred DIR --gt DIR [--out FILE.npy] [--spacing Z Y X]
+    python tools/compute_metrics.py --pred DIR --gt DIR [--out FILE.npy] [--spacing Z Y X] [--labels 1,2,...]
+
+--labels scores one region per listed label (e.g. the nine organs of a CT label map) instead of the BraTS regions; any number of them.
 
 Cases are the files of --pred that have a file of the same name in --gt.  Label volumes are read from .npy and .npz (the first
 array, or the one called "labels" / "seg" / "arr_0"); .nii / .nii.gz through nibabel or SimpleITK where one is installed, else through
@@ -61,14 +63,20 @@ def main(argv=None):
     ap.add_argument("--gt", required=True)
     ap.add_argument("--out")
     ap.add_argument("--spacing", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("Z", "Y", "X"))
+    ap.add_argument("--labels", default=None, help="comma-separated labels: one region per label instead of the BraTS regions")
     args = ap.parse_args(argv)
     from segmamba_amd import metrics
+    regions = metrics.BRATS_REGIONS
+    if args.labels is not None:
+        regions = tuple((int(v),) for v in args.labels.split(",") if v.strip())
+        if not regions or any(not 1 <= r[0] <= 255 for r in regions):
+            raise RuntimeError(f"--labels: labels in 1 .. 255 are required, got {args.labels!r}")
     names = case_files(args.pred, args.gt)
 
     def cases():
         for n in names:
             yield load_labels(os.path.join(args.pred, n)), load_labels(os.path.join(args.gt, n)), tuple(args.spacing)
-    results, mean, std = metrics.evaluate(cases())
+    results, mean, std = metrics.evaluate(cases(), regions, max_regions=None)
     for n, r in zip(names, results):
         print(n, r.tolist())
     print(results.shape)

@@ -1,13 +1,16 @@
 """Logits to label volumes on the device: the command-line form of the reference's steps between `maybe_mirror_and_predict` and the
 file on disk (4_predict.py:75-99).
 
-    python tools/finish_predictions.py --logits DIR --out DIR [--postprocess] [--spacing X Y Z]
+    python tools/finish_predictions.py --logits DIR --out DIR [--postprocess | --per-class] [--organs NAME,NAME,...] [--spacing X Y Z]
 
 Every .npy / .npz of --logits holds the (C, d, h, w) logits of one case (.npz: the array called "logits" / "arr_0", or the first one).
 A .npz may also carry the reference loader's properties as arrays of the same names (`shape_after_cropping_before_resample`,
 `bbox_used_for_cropping`, `shape_before_cropping`, and `spacing` for the header); without them the labels have the logits' shape.
 Writes <case>.nii.gz label volumes that tools/compute_metrics.py reads.  --postprocess keeps, per BraTS region, the largest component
-with its holes filled (segmamba_amd.postprocess.postprocess_labels)."""
+with its holes filled (segmamba_amd.postprocess.postprocess_labels).  --per-class keeps the largest component of every class of the
+label map (segmamba_amd.postprocess.keep_largest_per_class: one labelled pass for all classes).  --organs also writes
+<out>/<case>/<NAME>.nii.gz = `labels == i` for the i-th name (1-based) of the label map as written (the loop of the reference's
+light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:97-109)."""
 import argparse
 import os
 import sys
@@ -40,9 +43,15 @@ def main(argv=None):
     ap.add_argument("--logits", required=True)
     ap.add_argument("--out", required=True)
     ap.add_argument("--postprocess", action="store_true")
+    ap.add_argument("--per-class", action="store_true", help="keep the largest component of every class")
+    ap.add_argument("--organs", default=None, help="comma-separated organ names for labels 1, 2, ...: one file per organ and case")
     ap.add_argument("--spacing", type=float, nargs=3, default=None, metavar=("X", "Y", "Z"))
     args = ap.parse_args(argv)
+    if args.postprocess and args.per_class:
+        raise RuntimeError("--postprocess (per BraTS region) and --per-class exclude each other")
+    organs = None if args.organs is None else [v.strip() for v in args.organs.split(",") if v.strip()]
     from segmamba_amd import nifti, postprocess
+    from segmamba_amd.predictor import Predictor
     names = sorted(n for n in os.listdir(args.logits) if n.endswith((".npy", ".npz")))
     if not names:
         raise RuntimeError(f"no .npy / .npz file in {args.logits}")
@@ -55,10 +64,15 @@ def main(argv=None):
         labels = postprocess.labels_from_logits(np.ascontiguousarray(logits, dtype=np.float32), props)
         if args.postprocess:
             labels = postprocess.postprocess_labels(labels)
+        if args.per_class:
+            labels = postprocess.keep_largest_per_class(labels)
         path = os.path.join(args.out, n[:-4] + ".nii.gz")
         nifti.write_nifti(path, labels.cpu().numpy(), args.spacing or spacing or (1.0, 1.0, 1.0))
         print(path, tuple(labels.shape))
         written.append(path)
+        if organs is not None:
+            written += Predictor(None).save_organs_to_nii(labels, args.spacing or spacing or (1.0, 1.0, 1.0),
+                                                          os.path.join(args.out, n[:-4]), organs)
     return written
 
 
