@@ -457,6 +457,75 @@ int segm_instnorm_fwd(const segm_instnorm_fwd_args* args);
 int segm_instnorm_bwd(const segm_instnorm_bwd_args* args);
 size_t segm_instnorm_workspace_bytes(int32_t instances, int64_t spatial);
 
+/* The residual tail of a block with a projection skip (monai dynunet_block.py:98-111 with `downsample`):
+ *     y = act(IN(x) + IN(skip))
+ * in one apply pass per direction.  IN(skip) is never stored (forward: 4 tensors of traffic, not 6) and its gradient never
+ * parked (backward: 10, not 12).  The results - y, both mean / rstd pairs, dx, dskip - are bit-equal to
+ *     segm_instnorm_fwd(skip, act 0) -> residual;  segm_instnorm_fwd(x, residual, act)
+ * and their two backwards with dresidual wanted: IN(skip) and g = dy act'(.) are rounded to the type in registers where that
+ * sequence rounds them through memory, and every sum runs in the same order.  Both stated deviations above are inherited unchanged.
+ *   segm_instnorm_stats      the statistics pass over one tensor into `partials` (segm_instnorm_workspace_bytes()), which the
+ *                            caller keeps until segm_instnorm_tail_fwd has consumed them as skip_partials
+ *   segm_instnorm_tail_fwd   statistics of x (its own pass, or stats_partials as in segm_instnorm_fwd), then the apply pass;
+ *                            writes mean / rstd of x and skip_mean / skip_rstd.  workspace: segm_instnorm_workspace_bytes()
+ *   segm_instnorm_tail_bwd   y is required iff act != 0.  workspace: segm_instnorm_tail_workspace_bytes() (four sums per slab)
+ * Additive to ABI 10 (no existing struct or function changes). */
+typedef struct segm_instnorm_stats_args {
+    int32_t instances, dtype;
+    int64_t spatial;
+    const void* x;
+    int64_t x_instance_stride;   /* 0 = spatial */
+    void* partials;
+    size_t partials_bytes;
+    void* stream;
+} segm_instnorm_stats_args;
+
+typedef struct segm_instnorm_tail_fwd_args {
+    int32_t instances, dtype, act, reserved;
+    int64_t spatial;
+    float slope, eps;
+    const void* x;
+    const void* skip;
+    void* y;
+    float* mean;
+    float* rstd;
+    float* skip_mean;
+    float* skip_rstd;
+    const void* skip_partials;   /* written by segm_instnorm_stats(skip) with the same instances, spatial and dtype */
+    size_t skip_partials_bytes;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    int64_t x_instance_stride, skip_instance_stride, y_instance_stride;
+    const float* stats_partials; /* of x, as in segm_instnorm_fwd_args; or NULL */
+    int32_t stats_nparts, reserved2;
+} segm_instnorm_tail_fwd_args;
+
+typedef struct segm_instnorm_tail_bwd_args {
+    int32_t instances, dtype, act, reserved;
+    int64_t spatial;
+    float slope, reserved2;
+    const void* x;
+    const void* skip;
+    const void* dy;
+    const void* y;
+    const float* mean;
+    const float* rstd;
+    const float* skip_mean;
+    const float* skip_rstd;
+    void* dx;
+    void* dskip;
+    void* workspace;
+    size_t workspace_bytes;
+    void* stream;
+    int64_t x_instance_stride, skip_instance_stride, dy_instance_stride, y_instance_stride, dx_instance_stride, dskip_instance_stride;
+} segm_instnorm_tail_bwd_args;
+
+int segm_instnorm_stats(const segm_instnorm_stats_args* args);
+int segm_instnorm_tail_fwd(const segm_instnorm_tail_fwd_args* args);
+int segm_instnorm_tail_bwd(const segm_instnorm_tail_bwd_args* args);
+size_t segm_instnorm_tail_workspace_bytes(int32_t instances, int64_t spatial);
+
 /* ------------------------------------------------------------------------------------------------
  * Batched transpose (+ add): out[b, c, r] = in[b, r, c] (+ add[b, c, r]).
  * Replaces the transposing copies around a Mamba layer - `x.reshape(B, C, n).transpose(-1, -2)` feeding LayerNorm and

@@ -14,6 +14,15 @@
 //             K4 apply   dx = rstd (g - mean(g) - xhat mean(g xhat))
 // The activation mask is taken from y when a residual was added (v is not recomputable from x alone), else from xhat.
 //
+// The residual tail y = act(IN(x) + IN(s)) of a block with a projection skip s (segm_instnorm_stats / _tail_fwd / _tail_bwd, the TAIL
+// variants of K2 - K4) never stores IN(s) and never parks g:
+//   forward   K1 over s, K1 over x (unless its producer summed the statistics), K2' y = act(xhat + T(shat)), both statistics written
+//   backward  K3' the four sums  g, g xhat, T(g), T(g) shat  in one pass;  K4' dx and ds from T(g), g re-formed from dy and y
+// T(.) rounds to the tensor type in registers where the two-call sequence rounds through memory; slabs, streaming modes, packets in
+// flight, per-thread chains and the order over slabs are those of the passes replaced, the per-element arithmetic is shared with them:
+// the tail gives the bits of segm_instnorm_fwd(s) -> segm_instnorm_fwd(x, residual) and their backwards (tests/norm_tail_checks.py),
+// with 4 + 10 tensors of traffic per block instead of 6 + 12 and three launches fewer.  It inherits both deviations below unchanged.
+//
 // Two stated deviations (tests/norm_ref.py derives the per-element bounds, tests/norm_checks.py holds the kernels to them):
 //   * dx is rounded twice when dresidual is wanted in a 16-bit type behind a LeakyReLU: K3 parks g ROUNDED to the type and K4 forms
 //     dx from that rounded value, so dx carries rstd ulp(g) / 2 on top of its own final rounding (up to ~4 x the half-ulp bound of the
@@ -44,6 +53,10 @@ struct NormDev {
     float slope, eps;
     const float4* ext;     // forward: {count, sum, sum of squares, -} partials summed by the producer of x (conv3d_fwd.hip), or null
     int32_t next;          // per instance
+    // the residual tail (TAIL kernels): `res` / `rs` is the skip tensor s, un-normalised; its statistics, its partials, its gradient
+    float* mean3; float* rstd3;
+    float2* part3;
+    void* ds; int64_t dss;
 };
 
 // sum over the workgroup of two values; result valid in every thread
@@ -71,7 +84,7 @@ __device__ __forceinline__ void slab_range(const NormDev& P, int split, int64_t&
 }
 
 // merges the (sum, sumsq) partials of an instance into mean / rstd (every thread gets the result)
-__device__ __forceinline__ float2 merge_stats(const NormDev& P, int inst, float2* lds) {
+__device__ __forceinline__ float2 merge_stats(const NormDev& P, const float2* part, int inst, float2* lds) {
     if (threadIdx.x == 0) {
         float n = 0.f, mean = 0.f, m2 = 0.f;
         for (int s = 0; s < P.nsplit; ++s) {
@@ -79,7 +92,7 @@ __device__ __forceinline__ float2 merge_stats(const NormDev& P, int inst, float2
             slab_range(P, s, e0, e1);
             const float ns = (float)(e1 - e0);
             if (ns <= 0.f) continue;
-            const float2 p = P.part[(int64_t)inst * P.nsplit + s];
+            const float2 p = part[(int64_t)inst * P.nsplit + s];
             const float ms = p.x / ns;
             const float m2s = fmaxf(p.y - p.x * ms, 0.f);
             const float d = ms - mean, nt = n + ns;
@@ -186,14 +199,40 @@ __device__ __forceinline__ float act_fwd(float v, int act, float slope) {
     return v > 0.f ? v : v * slope;                      // relu: slope == 0
 }
 
-template <typename T, bool VEC, bool NT = false, int U = 2>
+// fp16 only: the compiler may fold the multiply that forms a value into its conversion to the type (v_fma_mixlo_f16: one rounding of
+// the exact product, not two) and chooses element by element.  A value pinned in a register before it is converted is rounded the
+// same way wherever it is formed - what makes the tail passes bit-equal to the passes they replace.  (bf16 and fp32 have no such form.)
+template <typename T> struct IsF16 { static constexpr bool value = false; };
+template <> struct IsF16<f16_t> { static constexpr bool value = true; };
+template <typename T> __device__ __forceinline__ void pin_f16(float& v) {
+#ifndef SEGM_EMU
+    if constexpr (IsF16<T>::value) asm volatile("" : "+v"(v));
+#endif
+}
+
+// the value a tensor of type T would have held
+template <typename T> __device__ __forceinline__ float round_to(float v) {
+    pin_f16<T>(v);
+    return to_f32(from_f32<T>(v));
+}
+
+// TAIL: `res` is the un-normalised skip s with the partials of its own statistics pass in part3; the pass adds IN(s) rounded to T,
+// the residual tensor the two-call sequence stores and reads back, and writes the statistics of both tensors
+template <typename T, bool VEC, bool NT = false, int U = 2, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock) inorm_fwd_apply_kernel(NormDev P) {
     using Pk = Pack<T, VEC>;
     __shared__ float2 lds[kWavesPerBlock];
     const int split = blockIdx.x, inst = blockIdx.y;
-    const float2 st = P.ext ? merge_ext(P, inst, lds) : merge_stats(P, inst, lds);
+    const float2 st = P.ext ? merge_ext(P, inst, lds) : merge_stats(P, P.part, inst, lds);
     const float mean = st.x, rstd = st.y;
     if (split == 0 && threadIdx.x == 0) { P.mean[inst] = mean; P.rstd[inst] = rstd; }
+    float rstd3 = 0.f, shift3 = 0.f;
+    if constexpr (TAIL) {
+        const float2 s3 = merge_stats(P, P.part3, inst, lds);
+        if (split == 0 && threadIdx.x == 0) { P.mean3[inst] = s3.x; P.rstd3[inst] = s3.y; }
+        rstd3 = s3.y;
+        shift3 = -s3.x * s3.y;
+    }
     const T* x = reinterpret_cast<const T*>(P.x) + (int64_t)inst * P.xs;
     const T* res = P.res ? reinterpret_cast<const T*>(P.res) + (int64_t)inst * P.rs : nullptr;
     T* y = reinterpret_cast<T*>(P.y) + (int64_t)inst * P.ys;
@@ -206,8 +245,10 @@ __global__ void __launch_bounds__(kBlock) inorm_fwd_apply_kernel(NormDev P) {
 #pragma unroll
         for (int j = 0; j < Pk::N; ++j) {
             float v = fmaf(a.v[j], rstd, shift);
-            if (res) v += r.v[j];
+            if constexpr (TAIL) v += round_to<T>(fmaf(r.v[j], rstd3, shift3));
+            else if (res) v += r.v[j];
             a.v[j] = act_fwd(v, P.act, slope);
+            pin_f16<T>(a.v[j]);
         }
     };
     int64_t i = e0 + (int64_t)threadIdx.x * Pk::N;
@@ -245,12 +286,17 @@ __device__ __forceinline__ void grad_through_act(Pk& g, const Pk& xh, const Pk& 
     }
 }
 
-template <typename T, bool VEC, bool NT = false, int U = 2>
+// TAIL: one pass for both branches of a residual tail.  Beside sum g and sum g xhat of x it sums gr = g rounded to T and gr shat for the
+// skip s (`res`), what the statistics pass of the skip's own InstanceNorm sums from the parked g; nothing is parked
+template <typename T, bool VEC, bool NT = false, int U = 2, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock) inorm_bwd_stats_kernel(NormDev P) {
     using Pk = Pack<T, VEC>;
     __shared__ float2 lds[kWavesPerBlock];
     const int split = blockIdx.x, inst = blockIdx.y;
     const T* x = reinterpret_cast<const T*>(P.x) + (int64_t)inst * P.xs;
+    const T* sk = TAIL ? reinterpret_cast<const T*>(P.res) + (int64_t)inst * P.rs : nullptr;
+    const float rstd3 = TAIL ? P.rstd3[inst] : 0.f;
+    const float shift3 = TAIL ? -P.mean3[inst] * rstd3 : 0.f;
     const T* dy = reinterpret_cast<const T*>(P.dy) + (int64_t)inst * P.dys;
     const T* ym = P.ymask ? reinterpret_cast<const T*>(P.ymask) + (int64_t)inst * P.ys : nullptr;
     T* dres = P.dres ? reinterpret_cast<T*>(P.dres) + (int64_t)inst * P.drs : nullptr;
@@ -260,59 +306,109 @@ __global__ void __launch_bounds__(kBlock) inorm_bwd_stats_kernel(NormDev P) {
     const bool use_y = ym != nullptr;
     int64_t e0, e1;
     slab_range(P, split, e0, e1);
-    float sg[U], sgx[U];
+    float sg[U], sgx[U], sh[U], shs[U];
 #pragma unroll
-    for (int k = 0; k < U; ++k) sg[k] = sgx[k] = 0.f;
+    for (int k = 0; k < U; ++k) sg[k] = sgx[k] = sh[k] = shs[k] = 0.f;
     const int64_t step = (int64_t)kBlock * Pk::N;
     // (x, dy and y are read again by the apply pass: never non-temporal; the parked g is)
     auto one = [&](Pk& xa, Pk& ga, const Pk& ya, float& a, float& b, int64_t at) {
 #pragma unroll
         for (int j = 0; j < Pk::N; ++j) xa.v[j] = fmaf(xa.v[j], rstd, shift);
         grad_through_act(ga, xa, ya, use_y, P.act, slope);
+        if (TAIL || dres) {                                 // g is about to be rounded to the type
+#pragma unroll
+            for (int j = 0; j < Pk::N; ++j) pin_f16<T>(ga.v[j]);
+        }
 #pragma unroll
         for (int j = 0; j < Pk::N; ++j) { a += ga.v[j]; b = fmaf(ga.v[j], xa.v[j], b); }
         if (dres) ga.store(dres + at);
     };
+    // the skip branch: what `one` does in the skip's own pass (no activation), on the g that pass would read back
+    auto skip = [&](Pk& sa, const Pk& ga, float& a, float& b) {
+#pragma unroll
+        for (int j = 0; j < Pk::N; ++j) {
+            sa.v[j] = fmaf(sa.v[j], rstd3, shift3);
+            const float gr = round_to<T>(ga.v[j]);
+            a += gr;
+            b = fmaf(gr, sa.v[j], b);
+        }
+    };
     int64_t i = e0 + (int64_t)threadIdx.x * Pk::N;
     for (; i + (U - 1) * step < e1; i += U * step) {
-        Pk xa[U], ga[U], ya[U];
+        Pk xa[U], ga[U], ya[U], sa[TAIL ? U : 1];
 #pragma unroll
         for (int k = 0; k < U; ++k) { xa[k].template load<NT>(x + i + k * step); ga[k].template load<NT>(dy + i + k * step); }
         if (use_y && P.act) {
 #pragma unroll
             for (int k = 0; k < U; ++k) ya[k].template load<NT>(ym + i + k * step);
         }
+        if constexpr (TAIL) {
 #pragma unroll
-        for (int k = 0; k < U; ++k) one(xa[k], ga[k], ya[k], sg[k], sgx[k], i + k * step);
+            for (int k = 0; k < U; ++k) sa[k].template load<NT>(sk + i + k * step);
+        }
+#pragma unroll
+        for (int k = 0; k < U; ++k) {
+            one(xa[k], ga[k], ya[k], sg[k], sgx[k], i + k * step);
+            if constexpr (TAIL) skip(sa[k], ga[k], sh[k], shs[k]);
+        }
     }
     for (; i < e1; i += step) {
         Pk xa, ga, ya;
         xa.template load<NT>(x + i); ga.template load<NT>(dy + i);
         if (use_y && P.act) ya.template load<NT>(ym + i);
         one(xa, ga, ya, sg[0], sgx[0], i);
+        if constexpr (TAIL) {
+            Pk sa;
+            sa.template load<NT>(sk + i);
+            skip(sa, ga, sh[0], shs[0]);
+        }
     }
     float a = 0.f, b = 0.f;
 #pragma unroll
     for (int k = 0; k < U; ++k) { a += sg[k]; b += sgx[k]; }
     const float2 r = block_sum2(a, b, lds);
     if (threadIdx.x == 0) P.part[(int64_t)inst * P.nsplit + split] = r;
+    if constexpr (TAIL) {
+        float c = 0.f, d = 0.f;
+#pragma unroll
+        for (int k = 0; k < U; ++k) { c += sh[k]; d += shs[k]; }
+        const float2 r3 = block_sum2(c, d, lds);
+        if (threadIdx.x == 0) P.part3[(int64_t)inst * P.nsplit + split] = r3;
+    }
 }
 
-template <typename T, bool VEC, bool NT = false, int U = 1>
+// the means of an instance's (sum g, sum g xhat) partials, summed by thread 0 in slab order into *out
+__device__ __forceinline__ void mean_partials(const NormDev& P, const float2* part, int inst, float2* out) {
+    float a = 0.f, b = 0.f;
+    for (int s = 0; s < P.nsplit; ++s) {
+        const float2 p = part[(int64_t)inst * P.nsplit + s];
+        a += p.x; b += p.y;
+    }
+    *out = make_float2(a / (float)P.S, b / (float)P.S);
+}
+
+__device__ __forceinline__ float norm_dx(float g, float xh, float mg, float mgx, float rstd) {
+    return rstd * (g - mg - xh * mgx);
+}
+
+// TAIL: g is formed from dy and y and rounded to T in registers (the value the two-call sequence parks and reads back); from it
+// dx for x and ds for the skip s (`res`), each with its own statistics and partials
+template <typename T, bool VEC, bool NT = false, int U = 1, bool TAIL = false>
 __global__ void __launch_bounds__(kBlock) inorm_bwd_apply_kernel(NormDev P) {
     using Pk = Pack<T, VEC>;
     __shared__ float2 lds[kWavesPerBlock];
     const int split = blockIdx.x, inst = blockIdx.y;
     if (threadIdx.x == 0) {
-        float a = 0.f, b = 0.f;
-        for (int s = 0; s < P.nsplit; ++s) {
-            const float2 p = P.part[(int64_t)inst * P.nsplit + s];
-            a += p.x; b += p.y;
-        }
-        lds[0] = make_float2(a / (float)P.S, b / (float)P.S);
+        mean_partials(P, P.part, inst, &lds[0]);
+        if constexpr (TAIL) mean_partials(P, P.part3, inst, &lds[1]);
     }
     __syncthreads();
     const float mg = lds[0].x, mgx = lds[0].y;
+    const float mg3 = TAIL ? lds[1].x : 0.f, mgx3 = TAIL ? lds[1].y : 0.f;
+    const T* sk = TAIL ? reinterpret_cast<const T*>(P.res) + (int64_t)inst * P.rs : nullptr;
+    T* ds = TAIL ? reinterpret_cast<T*>(P.ds) + (int64_t)inst * P.dss : nullptr;
+    const float rstd3 = TAIL ? P.rstd3[inst] : 0.f;
+    const float shift3 = TAIL ? -P.mean3[inst] * rstd3 : 0.f;
     const T* x = reinterpret_cast<const T*>(P.x) + (int64_t)inst * P.xs;
     const T* dy = reinterpret_cast<const T*>(P.dy) + (int64_t)inst * P.dys;
     const T* ym = P.ymask ? reinterpret_cast<const T*>(P.ymask) + (int64_t)inst * P.ys : nullptr;
@@ -330,11 +426,25 @@ __global__ void __launch_bounds__(kBlock) inorm_bwd_apply_kernel(NormDev P) {
         for (int j = 0; j < Pk::N; ++j) xa.v[j] = fmaf(xa.v[j], rstd, shift);
         if (!gsrc) grad_through_act(ga, xa, ya, use_y, P.act, slope);
 #pragma unroll
-        for (int j = 0; j < Pk::N; ++j) ga.v[j] = rstd * (ga.v[j] - mg - xa.v[j] * mgx);
+        for (int j = 0; j < Pk::N; ++j) { ga.v[j] = norm_dx(ga.v[j], xa.v[j], mg, mgx, rstd); pin_f16<T>(ga.v[j]); }
+    };
+    // both branches from the rounded g: sa -> ds, ga -> dx
+    auto both = [&](Pk& xa, Pk& ga, const Pk& ya, Pk& sa) {
+#pragma unroll
+        for (int j = 0; j < Pk::N; ++j) xa.v[j] = fmaf(xa.v[j], rstd, shift);
+        grad_through_act(ga, xa, ya, use_y, P.act, slope);
+#pragma unroll
+        for (int j = 0; j < Pk::N; ++j) {
+            const float gr = round_to<T>(ga.v[j]);
+            ga.v[j] = norm_dx(gr, xa.v[j], mg, mgx, rstd);
+            sa.v[j] = norm_dx(gr, fmaf(sa.v[j], rstd3, shift3), mg3, mgx3, rstd3);
+            pin_f16<T>(ga.v[j]);
+            pin_f16<T>(sa.v[j]);
+        }
     };
     int64_t i = e0 + (int64_t)threadIdx.x * Pk::N;
     for (; i + (U - 1) * step < e1; i += U * step) {
-        Pk xa[U], ga[U], ya[U];
+        Pk xa[U], ga[U], ya[U], sa[TAIL ? U : 1];
 #pragma unroll
         for (int k = 0; k < U; ++k) {
             xa[k].template load<NT>(x + i + k * step);
@@ -345,9 +455,16 @@ __global__ void __launch_bounds__(kBlock) inorm_bwd_apply_kernel(NormDev P) {
 #pragma unroll
             for (int k = 0; k < U; ++k) ya[k].template load<NT>(ym + i + k * step);
         }
+        if constexpr (TAIL) {
+#pragma unroll
+            for (int k = 0; k < U; ++k) sa[k].template load<NT>(sk + i + k * step);
+        }
 #pragma unroll
         for (int k = 0; k < U; ++k) {
-            one(xa[k], ga[k], ya[k]);
+            if constexpr (TAIL) {
+                both(xa[k], ga[k], ya[k], sa[k]);
+                sa[k].template store<NT>(ds + i + k * step);
+            } else one(xa[k], ga[k], ya[k]);
             ga[k].template store<NT>(dx + i + k * step);
         }
     }
@@ -360,7 +477,12 @@ __global__ void __launch_bounds__(kBlock) inorm_bwd_apply_kernel(NormDev P) {
                 ga.template load<NT>(dy + i);
                 if (use_y && P.act) ya.template load<NT>(ym + i);
             }
-            one(xa, ga, ya);
+            if constexpr (TAIL) {
+                Pk sa;
+                sa.template load<NT>(sk + i);
+                both(xa, ga, ya, sa);
+                sa.template store<NT>(ds + i);
+            } else one(xa, ga, ya);
             ga.template store<NT>(dx + i);
         }
     }
@@ -440,6 +562,48 @@ static int launch_norm_bwd(NormDev& P, int instances, bool vec, hipStream_t st) 
     return (int)hipGetLastError();
 }
 
+// the statistics pass alone (the skip of a residual tail: its partials wait for the tail's apply pass)
+template <typename T>
+static int launch_norm_stats(NormDev& P, int instances, bool vec, hipStream_t st) {
+    dim3 grid(P.nsplit, instances);
+    if (vec) hipLaunchKernelGGL((inorm_fwd_stats_kernel<T, true>), grid, dim3(kBlock), 0, st, P);
+    else hipLaunchKernelGGL((inorm_fwd_stats_kernel<T, false>), grid, dim3(kBlock), 0, st, P);
+    return (int)hipGetLastError();
+}
+
+// the tail passes stream as the passes they replace: the same slabs, modes and packets in flight
+template <typename T>
+static int launch_norm_tail_fwd(NormDev& P, int instances, bool vec, hipStream_t st) {
+    dim3 grid(P.nsplit, instances);
+    const int mode = vec ? norm_mode(instances, P.S, sizeof(T)) : 0;
+    if (vec) {
+        if (!P.ext) hipLaunchKernelGGL((inorm_fwd_stats_kernel<T, true>), grid, dim3(kBlock), 0, st, P);
+        if (mode) hipLaunchKernelGGL((inorm_fwd_apply_kernel<T, true, true, 4, true>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((inorm_fwd_apply_kernel<T, true, false, 2, true>), grid, dim3(kBlock), 0, st, P);
+    } else {
+        if (!P.ext) hipLaunchKernelGGL((inorm_fwd_stats_kernel<T, false>), grid, dim3(kBlock), 0, st, P);
+        hipLaunchKernelGGL((inorm_fwd_apply_kernel<T, false, false, 2, true>), grid, dim3(kBlock), 0, st, P);
+    }
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static int launch_norm_tail_bwd(NormDev& P, int instances, bool vec, hipStream_t st) {
+    dim3 grid(P.nsplit, instances);
+    const int mode = vec ? norm_mode(instances, P.S, sizeof(T)) : 0;
+    if (vec) {
+        if (mode == 2) hipLaunchKernelGGL((inorm_bwd_stats_kernel<T, true, true, 4, true>), grid, dim3(kBlock), 0, st, P);
+        else if (mode == 1) hipLaunchKernelGGL((inorm_bwd_stats_kernel<T, true, false, 4, true>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((inorm_bwd_stats_kernel<T, true, false, 2, true>), grid, dim3(kBlock), 0, st, P);
+        if (mode) hipLaunchKernelGGL((inorm_bwd_apply_kernel<T, true, true, 4, true>), grid, dim3(kBlock), 0, st, P);
+        else hipLaunchKernelGGL((inorm_bwd_apply_kernel<T, true, false, 1, true>), grid, dim3(kBlock), 0, st, P);
+    } else {
+        hipLaunchKernelGGL((inorm_bwd_stats_kernel<T, false, false, 2, true>), grid, dim3(kBlock), 0, st, P);
+        hipLaunchKernelGGL((inorm_bwd_apply_kernel<T, false, false, 1, true>), grid, dim3(kBlock), 0, st, P);
+    }
+    return (int)hipGetLastError();
+}
+
 static int vec_width(int dtype) { return dtype == SEGM_F32 ? 4 : 8; }
 
 }  // namespace segm
@@ -509,4 +673,88 @@ extern "C" int segm_instnorm_bwd(const segm_instnorm_bwd_args* a) {
     if (a->dtype == SEGM_F32) return launch_norm_bwd<float>(P, a->instances, vec, st);
     if (a->dtype == SEGM_F16) return launch_norm_bwd<f16_t>(P, a->instances, vec, st);
     return launch_norm_bwd<bf16_t>(P, a->instances, vec, st);
+}
+
+// ---- the residual tail  y = act(IN(x) + IN(skip))  of a block with a projection skip ----------------------------------------------
+//   forward   K1 over the skip (segm_instnorm_stats), K1 over x unless its producer summed the statistics, then ONE apply pass
+//             (the skip's normalised value is rounded to the type in registers, never stored): 4 tensors of traffic, not 6
+//   backward  ONE statistics pass (the four sums of both branches), ONE apply pass writing dx and dskip: 10 tensors, not 12
+// Every sum is accumulated in the order of the two-call sequence and every element goes through the same helpers: the results are
+// bit-equal to segm_instnorm_fwd(skip) -> segm_instnorm_fwd(x, residual) and their backwards with dresidual (tests/norm_tail_checks.py).
+extern "C" size_t segm_instnorm_tail_workspace_bytes(int32_t instances, int64_t spatial) {
+    return 2 * segm_instnorm_workspace_bytes(instances, spatial);
+}
+
+extern "C" int segm_instnorm_stats(const segm_instnorm_stats_args* a) {
+    if (!a) return SEGM_E_NULL;
+    int rc = norm_common(a->instances, a->spatial, a->dtype, 0, a->partials, a->partials_bytes);
+    if (rc != SEGM_OK) return rc;
+    if (!a->x) return SEGM_E_NULL;
+    NormDev P;
+    memset(&P, 0, sizeof(P));
+    P.x = a->x; P.part = (float2*)a->partials; P.S = a->spatial;
+    if (!norm_stride(a->x_instance_stride, a->spatial, P.xs)) return SEGM_E_SHAPE;
+    const int vn = vec_width(a->dtype);
+    const bool vec = a->spatial % vn == 0 && P.xs % vn == 0 && aligned16(a->x);
+    norm_plan(a->instances, a->spatial, vn, P.nsplit, P.slab);
+    hipStream_t st = (hipStream_t)a->stream;
+    if (a->dtype == SEGM_F32) return launch_norm_stats<float>(P, a->instances, vec, st);
+    if (a->dtype == SEGM_F16) return launch_norm_stats<f16_t>(P, a->instances, vec, st);
+    return launch_norm_stats<bf16_t>(P, a->instances, vec, st);
+}
+
+extern "C" int segm_instnorm_tail_fwd(const segm_instnorm_tail_fwd_args* a) {
+    if (!a) return SEGM_E_NULL;
+    int rc = norm_common(a->instances, a->spatial, a->dtype, a->act, a->workspace, a->workspace_bytes);
+    if (rc != SEGM_OK) return rc;
+    if (!a->x || !a->skip || !a->y || !a->mean || !a->rstd || !a->skip_mean || !a->skip_rstd) return SEGM_E_NULL;
+    if (!a->skip_partials || a->skip_partials_bytes < segm_instnorm_workspace_bytes(a->instances, a->spatial)) return SEGM_E_WORKSPACE;
+    NormDev P;
+    memset(&P, 0, sizeof(P));
+    P.x = a->x; P.res = a->skip; P.y = a->y; P.mean = a->mean; P.rstd = a->rstd; P.mean3 = a->skip_mean; P.rstd3 = a->skip_rstd;
+    P.part = (float2*)a->workspace; P.part3 = (float2*)a->skip_partials;
+    P.S = a->spatial; P.act = a->act; P.slope = a->slope; P.eps = a->eps;
+    if (a->stats_partials) {
+        if (a->stats_nparts <= 0 || ((uintptr_t)a->stats_partials & 15)) return SEGM_E_SHAPE;
+        P.ext = (const float4*)a->stats_partials; P.next = a->stats_nparts;
+    }
+    if (!norm_stride(a->x_instance_stride, a->spatial, P.xs) || !norm_stride(a->skip_instance_stride, a->spatial, P.rs) ||
+        !norm_stride(a->y_instance_stride, a->spatial, P.ys))
+        return SEGM_E_SHAPE;
+    const int vn = vec_width(a->dtype);
+    const bool vec = a->spatial % vn == 0 && P.xs % vn == 0 && P.rs % vn == 0 && P.ys % vn == 0 && aligned16(a->x) && aligned16(a->y) && aligned16(a->skip);
+    norm_plan(a->instances, a->spatial, vn, P.nsplit, P.slab);
+    hipStream_t st = (hipStream_t)a->stream;
+    if (a->dtype == SEGM_F32) return launch_norm_tail_fwd<float>(P, a->instances, vec, st);
+    if (a->dtype == SEGM_F16) return launch_norm_tail_fwd<f16_t>(P, a->instances, vec, st);
+    return launch_norm_tail_fwd<bf16_t>(P, a->instances, vec, st);
+}
+
+extern "C" int segm_instnorm_tail_bwd(const segm_instnorm_tail_bwd_args* a) {
+    if (!a) return SEGM_E_NULL;
+    int rc = norm_common(a->instances, a->spatial, a->dtype, a->act, a->workspace, a->workspace_bytes);
+    if (rc != SEGM_OK) return rc;
+    if (a->workspace_bytes < segm_instnorm_tail_workspace_bytes(a->instances, a->spatial)) return SEGM_E_WORKSPACE;    // four sums per slab
+    if (!a->x || !a->skip || !a->dy || !a->dx || !a->dskip || !a->mean || !a->rstd || !a->skip_mean || !a->skip_rstd) return SEGM_E_NULL;
+    if (a->act && !a->y) return SEGM_E_NULL;             // a residual was added: the activation mask comes from y
+    NormDev P;
+    memset(&P, 0, sizeof(P));
+    P.x = a->x; P.res = a->skip; P.dy = a->dy; P.ymask = a->act ? a->y : nullptr; P.dx = a->dx; P.ds = a->dskip;
+    P.mean = (float*)a->mean; P.rstd = (float*)a->rstd; P.mean3 = (float*)a->skip_mean; P.rstd3 = (float*)a->skip_rstd;
+    P.part = (float2*)a->workspace;
+    P.part3 = P.part + (size_t)a->instances * kNormMaxSplit;
+    P.S = a->spatial; P.act = a->act; P.slope = a->slope; P.eps = 0.f;
+    if (!norm_stride(a->x_instance_stride, a->spatial, P.xs) || !norm_stride(a->skip_instance_stride, a->spatial, P.rs) ||
+        !norm_stride(a->dy_instance_stride, a->spatial, P.dys) || !norm_stride(a->y_instance_stride, a->spatial, P.ys) ||
+        !norm_stride(a->dx_instance_stride, a->spatial, P.dxs) || !norm_stride(a->dskip_instance_stride, a->spatial, P.dss))
+        return SEGM_E_SHAPE;
+    const int vn = vec_width(a->dtype);
+    const bool vec = a->spatial % vn == 0 && P.xs % vn == 0 && P.rs % vn == 0 && P.dys % vn == 0 && P.ys % vn == 0 && P.dxs % vn == 0 &&
+                     P.dss % vn == 0 && aligned16(a->x) && aligned16(a->skip) && aligned16(a->dy) && aligned16(a->dx) && aligned16(a->dskip) &&
+                     (!P.ymask || aligned16(P.ymask));
+    norm_plan(a->instances, a->spatial, vn, P.nsplit, P.slab);
+    hipStream_t st = (hipStream_t)a->stream;
+    if (a->dtype == SEGM_F32) return launch_norm_tail_bwd<float>(P, a->instances, vec, st);
+    if (a->dtype == SEGM_F16) return launch_norm_tail_bwd<f16_t>(P, a->instances, vec, st);
+    return launch_norm_tail_bwd<bf16_t>(P, a->instances, vec, st);
 }

@@ -11,7 +11,8 @@ parameters, no running statistics, eps = 1e-5, biased variance.
 On the GPU every call is two launches of the library's own kernels per direction (csrc/instnorm.hip:
 statistics, then normalise + residual + activation in one pass; the backward likewise) instead of the three to four
 ATen kernels per direction the reference runs (batch_norm statistics / transform, add, leaky_relu and their
-backward counterparts: 41 ms of a 283 ms training step, profiles/r01_bench_step_kernels_v5.txt).  CPU tensors
+backward counterparts: 41 ms of a 283 ms training step, profiles/r01_bench_step_kernels_v5.txt).  The tail of a residual block
+with a projection skip, act(IN(x) + IN(skip)), is one node with one apply pass per direction (`instance_norm_tail`).  CPU tensors
 (unit tests of the host logic) take the ATen expression of the same math.
 """
 from __future__ import annotations
@@ -50,6 +51,56 @@ class _InstNormAct(torch.autograd.Function):
         dx, dres = ops_raw.instnorm_bwd(L.get_lib(), x, dy, mean, rstd, y, act, slope,
                                         want_dresidual=has_res and ctx.needs_input_grad[1])
         return dx, dres, None, None, None, None
+
+
+class _InstNormTail(torch.autograd.Function):
+    """y = act(IN(x) + IN(skip)), the tail of a residual block with a projection skip, through segm_instnorm_stats /
+    segm_instnorm_tail_fwd / segm_instnorm_tail_bwd: IN(skip) is never stored and its gradient never parked (4 + 10 tensors of
+    traffic per block, not 6 + 12), bit-equal to the two _InstNormAct nodes it stands for."""
+
+    @staticmethod
+    def forward(ctx, x, skip, act, slope, eps, stats=None):
+        from . import lib as L, ops_raw
+        if not ops_raw.channel_dense(x):
+            x = x.contiguous()
+        if not ops_raw.channel_dense(skip):
+            skip = skip.contiguous()
+        lib = L.get_lib()
+        skip_stats = ops_raw.instnorm_fwd(lib, skip, stats_only=True)
+        y, mean, rstd = ops_raw.instnorm_fwd(lib, x, None, act, slope, eps, stats=stats, skip=skip, skip_stats=skip_stats)
+        ctx.save_for_backward(x, skip, y if act != "none" else None, mean, rstd, skip_stats.mean, skip_stats.rstd)
+        ctx.cfg = (act, slope)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        from . import lib as L, ops_raw
+        x, skip, y, mean, rstd, skip_mean, skip_rstd = ctx.saved_tensors
+        act, slope = ctx.cfg
+        dx, dskip = ops_raw.instnorm_tail_bwd(L.get_lib(), x, skip, dy, mean, rstd, skip_mean, skip_rstd, y, act, slope)
+        return dx, dskip, None, None, None, None
+
+
+_NORM_TAIL = os.environ.get("SEGM_NORM_TAIL", "1") != "0"
+
+
+def tail_route(x: torch.Tensor, skip: torch.Tensor) -> bool:
+    """whether instance_norm_tail(x, skip) runs as one node: SEGM_NORM_TAIL is not 0, device tensors of one dtype, and the skip
+    wants its gradient whenever x does (the two-node form rounds g only when the residual's gradient is asked for)"""
+    from . import lib as L
+    return (_NORM_TAIL and L.on_device(x) and L.on_device(skip) and skip.dtype == x.dtype and skip.shape == x.shape
+            and (skip.requires_grad or not x.requires_grad or not torch.is_grad_enabled()))
+
+
+def instance_norm_tail(x: torch.Tensor, skip: torch.Tensor, act: str = "leaky_relu", slope: float = 0.01, eps: float = 1e-5,
+                       stats: torch.Tensor | None = None) -> torch.Tensor:
+    """y = act(IN(x) + IN(skip)) for x, skip of shape (B, C, D, H, W); `stats` as in instance_norm_act, for x.  One autograd node
+    on the device (see tail_route), the two instance_norm_act calls otherwise."""
+    if act not in ("none", "relu", "leaky_relu"):
+        raise ValueError(f"unknown activation {act!r}")
+    if tail_route(x, skip):
+        return _InstNormTail.apply(x, skip, act, slope, eps, stats)
+    return instance_norm_act(x, act, slope, eps, residual=instance_norm_act(skip, "none", eps=eps), stats=stats)
 
 
 def instance_norm_act(x: torch.Tensor, act: str = "none", slope: float = 0.01, eps: float = 1e-5,

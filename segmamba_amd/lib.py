@@ -162,6 +162,38 @@ class InstNormBwdArgs(C.Structure):
     ]
 
 
+class InstNormStatsArgs(C.Structure):
+    _fields_ = [
+        ("instances", C.c_int32), ("dtype", C.c_int32), ("spatial", C.c_int64),
+        ("x", C.c_void_p), ("x_instance_stride", C.c_int64),
+        ("partials", C.c_void_p), ("partials_bytes", C.c_size_t), ("stream", C.c_void_p),
+    ]
+
+
+class InstNormTailFwdArgs(C.Structure):
+    _fields_ = [
+        ("instances", C.c_int32), ("dtype", C.c_int32), ("act", C.c_int32), ("reserved", C.c_int32),
+        ("spatial", C.c_int64), ("slope", C.c_float), ("eps", C.c_float),
+        ("x", C.c_void_p), ("skip", C.c_void_p), ("y", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p),
+        ("skip_mean", C.c_void_p), ("skip_rstd", C.c_void_p), ("skip_partials", C.c_void_p), ("skip_partials_bytes", C.c_size_t),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p),
+        ("x_instance_stride", C.c_int64), ("skip_instance_stride", C.c_int64), ("y_instance_stride", C.c_int64),
+        ("stats_partials", C.c_void_p), ("stats_nparts", C.c_int32), ("reserved2", C.c_int32),
+    ]
+
+
+class InstNormTailBwdArgs(C.Structure):
+    _fields_ = [
+        ("instances", C.c_int32), ("dtype", C.c_int32), ("act", C.c_int32), ("reserved", C.c_int32),
+        ("spatial", C.c_int64), ("slope", C.c_float), ("reserved2", C.c_float),
+        ("x", C.c_void_p), ("skip", C.c_void_p), ("dy", C.c_void_p), ("y", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p),
+        ("skip_mean", C.c_void_p), ("skip_rstd", C.c_void_p), ("dx", C.c_void_p), ("dskip", C.c_void_p),
+        ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p),
+        ("x_instance_stride", C.c_int64), ("skip_instance_stride", C.c_int64), ("dy_instance_stride", C.c_int64),
+        ("y_instance_stride", C.c_int64), ("dx_instance_stride", C.c_int64), ("dskip_instance_stride", C.c_int64),
+    ]
+
+
 class LayerNormArgs(C.Structure):
     _fields_ = [
         ("batch", C.c_int32), ("channels", C.c_int32), ("dtype", C.c_int32), ("reserved", C.c_int32),
@@ -291,6 +323,7 @@ EXPORTS = (
     "segm_conv3d_k3_cube_wgrad", "segm_conv3d_k3_cube_wgrad_workspace_bytes", "segm_gather16",
     "segm_conv3d_k3_cube_pack_multi", "segm_conv3d_k3_cube_stats_parts",
     "segm_instnorm_fwd", "segm_instnorm_bwd", "segm_instnorm_workspace_bytes", "segm_transpose_add", "segm_depth_to_space2",
+    "segm_instnorm_stats", "segm_instnorm_tail_fwd", "segm_instnorm_tail_bwd", "segm_instnorm_tail_workspace_bytes",
     "segm_layernorm_tokens_fwd", "segm_layernorm_tokens_bwd", "segm_layernorm_tokens_workspace_bytes",
     "segm_sgd_clip_step", "segm_sgd_clip_step_workspace_bytes", "segm_cross_entropy", "segm_cross_entropy_partials",
     "segm_causal_conv1d_update", "segm_selective_state_update", "segm_linear_rows", "segm_pointwise_cf", "segm_stem_conv_fwd",
@@ -654,6 +687,10 @@ class SegmLib:
         sig("segm_instnorm_fwd", [C.POINTER(InstNormFwdArgs)], C.c_int)
         sig("segm_instnorm_bwd", [C.POINTER(InstNormBwdArgs)], C.c_int)
         sig("segm_instnorm_workspace_bytes", [C.c_int32, C.c_int64], C.c_size_t)
+        sig("segm_instnorm_stats", [C.POINTER(InstNormStatsArgs)], C.c_int)
+        sig("segm_instnorm_tail_fwd", [C.POINTER(InstNormTailFwdArgs)], C.c_int)
+        sig("segm_instnorm_tail_bwd", [C.POINTER(InstNormTailBwdArgs)], C.c_int)
+        sig("segm_instnorm_tail_workspace_bytes", [C.c_int32, C.c_int64], C.c_size_t)
         sig("segm_transpose_add", [C.POINTER(TransposeArgs)], C.c_int)
         sig("segm_depth_to_space2", [C.POINTER(D2sArgs)], C.c_int)
         sig("segm_layernorm_tokens_fwd", [C.POINTER(LayerNormArgs)], C.c_int)

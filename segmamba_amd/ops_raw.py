@@ -765,31 +765,66 @@ def _norm_geom(x):
     return inst, x.numel() // inst
 
 
-def instnorm_fwd(lib: L.SegmLib, x, residual=None, act="none", slope=0.01, eps=1e-5, stats=None):
+class NormStats:
+    """The statistics pass of one tensor, waiting for the apply pass of a residual tail: `partials` as segm_instnorm_stats wrote them;
+    `mean` / `rstd` (fp32, B * C) are filled in by the tail's forward."""
+
+    def __init__(self, partials, mean, rstd):
+        self.partials, self.mean, self.rstd = partials, mean, rstd
+
+
+def instnorm_fwd(lib: L.SegmLib, x, residual=None, act="none", slope=0.01, eps=1e-5, stats=None, *, stats_only=False, skip=None,
+                 skip_stats=None):
     """-> (y, mean, rstd): y = act(IN(x) + residual); mean / rstd fp32 (B * C).
     stats: fp32 (B, C, nparts, 4) of {count, sum, sum of squares, -} partials summed by the producer of x (conv3d_k3_fwd's `stats`):
-    the statistics pass over x is skipped."""
+    the statistics pass over x is skipped.
+    The residual tail y = act(IN(x) + IN(skip)) in one apply pass (segm_instnorm_tail_fwd) takes two calls:
+      stats_only=True -> NormStats: the statistics pass over x alone (the skip), nothing applied;
+      skip=<the skip tensor>, skip_stats=<its NormStats> in place of a materialised residual -> (y, mean, rstd), and skip_stats.mean /
+      .rstd are filled in."""
     inst, S = _norm_geom(x)
+    if stats_only:
+        if residual is not None or stats is not None or skip is not None or skip_stats is not None:
+            raise RuntimeError("instnorm: stats_only takes x alone")
+        a = L.InstNormStatsArgs()
+        a.instances, a.dtype, a.spatial = inst, L.dtype_code(x), S
+        nbytes = lib.dll.segm_instnorm_workspace_bytes(inst, S)
+        part = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        a.x, a.x_instance_stride, a.partials, a.partials_bytes, a.stream = x.data_ptr(), instance_stride(x), part.data_ptr(), nbytes, L.stream_handle(x)
+        lib.check(lib.dll.segm_instnorm_stats(a), "instnorm_stats")
+        return NormStats(part, torch.empty(inst, dtype=torch.float32, device=x.device), torch.empty(inst, dtype=torch.float32, device=x.device))
     if stats is not None and (stats.dtype != torch.float32 or stats.dim() != 4 or stats.shape[0] * stats.shape[1] != inst or
                               stats.shape[3] != 4 or not stats.is_contiguous() or stats.device != x.device):
         raise RuntimeError("instnorm: stats must be a contiguous fp32 (B, C, nparts, 4) tensor on x's device")
     if residual is not None and (residual.shape != x.shape or residual.dtype != x.dtype or not channel_dense(residual)):
         raise RuntimeError("instnorm: residual must match x (shape, dtype, dense channels)")
-    a = L.InstNormFwdArgs()
+    if (skip is None) != (skip_stats is None) or (skip is not None and residual is not None):
+        raise RuntimeError("instnorm: a tail takes skip and skip_stats together, and no residual")
+    if skip is not None and (skip.shape != x.shape or skip.dtype != x.dtype or not channel_dense(skip) or skip.device != x.device
+                             or skip_stats.mean.numel() != inst):
+        raise RuntimeError("instnorm: skip must match x (shape, dtype, dense channels) and skip_stats must be its statistics")
+    a = L.InstNormFwdArgs() if skip is None else L.InstNormTailFwdArgs()
     a.instances, a.dtype, a.act, a.spatial = inst, L.dtype_code(x), ACT_CODES[act], S
     a.slope, a.eps = float(slope), float(eps)
     y = volume_empty(x.shape[0], x.shape[1], x.shape[2:], x.dtype, x.device)
     a.x_instance_stride, a.y_instance_stride = instance_stride(x), instance_stride(y)
-    a.residual_instance_stride = instance_stride(residual) if residual is not None else 0
     mean = torch.empty(inst, dtype=torch.float32, device=x.device)
     rstd = torch.empty(inst, dtype=torch.float32, device=x.device)
     ws_bytes = lib.dll.segm_instnorm_workspace_bytes(inst, S)
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-    a.x, a.residual, a.y = x.data_ptr(), (residual.data_ptr() if residual is not None else None), y.data_ptr()
+    a.x, a.y = x.data_ptr(), y.data_ptr()
     a.mean, a.rstd = mean.data_ptr(), rstd.data_ptr()
     a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), ws_bytes, L.stream_handle(x)
     if stats is not None:
         a.stats_partials, a.stats_nparts = stats.data_ptr(), stats.shape[2]
+    if skip is not None:
+        a.skip, a.skip_instance_stride = skip.data_ptr(), instance_stride(skip)
+        a.skip_mean, a.skip_rstd = skip_stats.mean.data_ptr(), skip_stats.rstd.data_ptr()
+        a.skip_partials, a.skip_partials_bytes = skip_stats.partials.data_ptr(), skip_stats.partials.numel()
+        lib.check(lib.dll.segm_instnorm_tail_fwd(a), "instnorm_tail_fwd")
+        return y, mean, rstd
+    a.residual = residual.data_ptr() if residual is not None else None
+    a.residual_instance_stride = instance_stride(residual) if residual is not None else 0
     lib.check(lib.dll.segm_instnorm_fwd(a), "instnorm_fwd")
     return y, mean, rstd
 
@@ -819,6 +854,35 @@ def instnorm_bwd(lib: L.SegmLib, x, dy, mean, rstd, y=None, act="none", slope=0.
     a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), ws_bytes, L.stream_handle(x)
     lib.check(lib.dll.segm_instnorm_bwd(a), "instnorm_bwd")
     return dx, dres
+
+
+def instnorm_tail_bwd(lib: L.SegmLib, x, skip, dy, mean, rstd, skip_mean, skip_rstd, y, act="leaky_relu", slope=0.01):
+    """-> (dx, dskip) of y = act(IN(x) + IN(skip)) in one statistics and one apply pass (segm_instnorm_tail_bwd); `y` is needed iff
+    act != none."""
+    inst, S = _norm_geom(x)
+    if dy.shape != x.shape or dy.dtype != x.dtype:
+        raise RuntimeError("instnorm: dy must match x")
+    if not channel_dense(dy):
+        dy = dy.contiguous()
+    for t in (skip, y):
+        if t is not None and (t.shape != x.shape or t.dtype != x.dtype or not channel_dense(t)):
+            raise RuntimeError("instnorm: skip and y must match x (shape, dtype, dense channels)")
+    a = L.InstNormTailBwdArgs()
+    a.instances, a.dtype, a.act, a.spatial = inst, L.dtype_code(x), ACT_CODES[act], S
+    a.slope = float(slope)
+    dx = volume_empty(x.shape[0], x.shape[1], x.shape[2:], x.dtype, x.device)
+    dskip = volume_empty(x.shape[0], x.shape[1], x.shape[2:], x.dtype, x.device)
+    a.x_instance_stride, a.skip_instance_stride, a.dy_instance_stride = instance_stride(x), instance_stride(skip), instance_stride(dy)
+    a.dx_instance_stride, a.dskip_instance_stride = instance_stride(dx), instance_stride(dskip)
+    a.y_instance_stride = instance_stride(y) if y is not None else 0
+    ws_bytes = lib.dll.segm_instnorm_tail_workspace_bytes(inst, S)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    a.x, a.skip, a.dy, a.y = x.data_ptr(), skip.data_ptr(), dy.data_ptr(), (y.data_ptr() if y is not None else None)
+    a.mean, a.rstd, a.skip_mean, a.skip_rstd = mean.data_ptr(), rstd.data_ptr(), skip_mean.data_ptr(), skip_rstd.data_ptr()
+    a.dx, a.dskip = dx.data_ptr(), dskip.data_ptr()
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), ws_bytes, L.stream_handle(x)
+    lib.check(lib.dll.segm_instnorm_tail_bwd(a), "instnorm_tail_bwd")
+    return dx, dskip
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -2803,7 +2867,7 @@ def _device_guard(fn):
 
 
 for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgrad", "conv3d_k3_fwd", "instnorm_fwd",
-              "instnorm_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
+              "instnorm_bwd", "instnorm_tail_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
               "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",

@@ -149,7 +149,12 @@ class UnetResBlock(nn.Module):
         out = fused_norm.instance_norm_act(out, act="leaky_relu", slope=self.NEG_SLOPE, eps=self.norm1.eps, stats=st)
         out, st = self.conv2(out, want_stats=True)
         if self.downsample:
-            residual = fused_norm.instance_norm_act(self.conv3(inp) if skip is None else skip, act="none", eps=self.norm3.eps)
+            if skip is None:
+                skip = self.conv3(inp)
+            if self.norm3.eps == self.norm2.eps and fused_norm.tail_route(out, skip):
+                # IN(out) + IN(skip) -> LeakyReLU as one node: the normalised skip is never stored (SEGM_NORM_TAIL=0: two nodes)
+                return fused_norm.instance_norm_tail(out, skip, act="leaky_relu", slope=self.NEG_SLOPE, eps=self.norm2.eps, stats=st)
+            residual = fused_norm.instance_norm_act(skip, act="none", eps=self.norm3.eps)
         else:
             residual = torch.cat(tuple(inp), dim=1) if isinstance(inp, (tuple, list)) else inp
         # IN(out) + residual -> LeakyReLU, one pass
