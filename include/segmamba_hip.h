@@ -958,6 +958,43 @@ typedef struct segm_border_distances_args {
 size_t segm_border_distances_workspace_bytes(int64_t voxels, int32_t n_items);
 int segm_border_distances(const segm_border_distances_args* args);
 
+/* What the surface metrics need of those lists, without the lists (additive to ABI 10; csrc/surface_stats.hip): medpy's asd / assd /
+ * hd / hd95 (light_training/evaluation/metric.py:314-383) and the voxel-counted surface Dice.  An ITEM is a list as above: the values
+ * d = sqrtf((float)edt[edt_plane[i]][v]) at the voxels v whose bit border_bit[i] is set in volume border_volume[i], formed as
+ * segm_border_distances forms them (the two entries agree bit for bit).  The items with item_group[i] == g form the JOINED list of
+ * group g (a region: prediction -> ground truth and back).  `out`, 16 x 4 + 16 x 2 doubles in device memory, all OVERWRITTEN:
+ *   out[4 i ..]      = count, sum of d (fp64), max d, number of voxels with d <= tolerance[i] (tolerance[i] < 0: none); an item
+ *                      without a set voxel gives 0, 0, 0, 0, as do the rows past n_items
+ *   out[64 + 2 g ..] = d at rank[g][0] and at rank[g][1] (0-based) of the ascending joined list; NaN for a rank that is negative or
+ *                      not below the group's count, and in the rows past n_groups
+ * Radix selection on the 32-bit key of the squared value (the int32, or the bits of the non-negative fp32), 8-bit digits: four passes
+ * over the border bytes, `edt` is read at set voxels only; sqrtf and the conversion are monotone, so the result equals "sort the
+ * list, index it".  An EDT sentinel (the target plane had no set voxel) is an ordinary key: callers pass live regions.
+ * Integer atomics on the histograms only; the fp64 sums go thread -> wave -> LDS -> one slot per workgroup, added by one workgroup in
+ * a fixed order: two calls are bit-equal.
+ * SEGM_E_SHAPE: voxels outside [1, SEGM_METRICS_MAX_VOXELS]; n_items or n_groups outside [1, SEGM_METRICS_MAX_PLANES]; an item_group
+ * outside [0, n_groups); a volume, bit or plane index out of range; a group whose items x voxels reach 2^32 (the histograms count in
+ * 32 bits); edt or out misaligned.  SEGM_E_NULL: a NULL pointer.  SEGM_E_DTYPE: fp32 not 0 or 1.  SEGM_E_WORKSPACE: workspace NULL,
+ * misaligned (8 bytes) or smaller than segm_border_stats_workspace_bytes (0 for arguments out of range).  Nothing is launched then. */
+typedef struct segm_border_stats_args {
+    int64_t voxels;                /* depth * height * width <= SEGM_METRICS_MAX_VOXELS */
+    int32_t n_volumes, n_planes, n_items, n_groups;
+    int32_t fp32, reserved;        /* edt is int32 (0) or fp32 (1) */
+    int32_t border_volume[SEGM_METRICS_MAX_PLANES];
+    int32_t border_bit[SEGM_METRICS_MAX_PLANES];
+    int32_t edt_plane[SEGM_METRICS_MAX_PLANES];
+    int32_t item_group[SEGM_METRICS_MAX_PLANES];
+    float tolerance[SEGM_METRICS_MAX_PLANES];
+    int64_t rank[SEGM_METRICS_MAX_PLANES][2];
+    const uint8_t* borders;        /* (n_volumes, voxels) bit planes */
+    const void* edt;               /* (n_planes, voxels) */
+    double* out;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_border_stats_args;
+size_t segm_border_stats_workspace_bytes(int64_t voxels, int32_t n_items);
+int segm_border_stats(const segm_border_stats_args* args);
+
 /* The same transform for sides up to SEGM_EDT_LONG_MAX_LINE, at a cost linear in the line length (additive to ABI 10;
  * csrc/edt_long.hip).  Meaning, planes, spacing rules and sentinels are those of segm_edt_sq, and the struct has its layout up to
  * `stream` with `reserved` taken by max_workgroups; segm_edt_sq itself keeps its limit and its refusals.

@@ -330,6 +330,7 @@ EXPORTS = (
     "segm_stem_conv_wgrad", "segm_stem_conv_wgrad_workspace_bytes", "segm_stem_conv_wgrad_workspace_bytes2", "segm_wgrad_gemm", "segm_wgrad_gemm_workspace_bytes",
     "segm_skinny_tn", "segm_skinny_tn_workspace_bytes", "segm_channel_sum", "segm_channel_sum_workspace_bytes", "segm_selective_scan_regular_shape",
     "segm_seg_regions", "segm_seg_regions_workspace_bytes", "segm_edt_sq", "segm_border_distances", "segm_border_distances_workspace_bytes",
+    "segm_border_stats", "segm_border_stats_workspace_bytes",
     "segm_edt_sq_long", "segm_edt_sq_long_workspace_bytes", "segm_planes_bbox",
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
@@ -402,6 +403,16 @@ class BorderDistancesArgs(C.Structure):
                 ("border_volume", C.c_int32 * METRICS_MAX_PLANES), ("border_bit", C.c_int32 * METRICS_MAX_PLANES),
                 ("edt_plane", C.c_int32 * METRICS_MAX_PLANES),
                 ("out_offset", C.c_int64 * METRICS_MAX_PLANES), ("out_count", C.c_int64 * METRICS_MAX_PLANES), ("out_capacity", C.c_int64),
+                ("borders", C.c_void_p), ("edt", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class BorderStatsArgs(C.Structure):
+    _fields_ = [("voxels", C.c_int64), ("n_volumes", C.c_int32), ("n_planes", C.c_int32), ("n_items", C.c_int32), ("n_groups", C.c_int32),
+                ("fp32", C.c_int32), ("reserved", C.c_int32),
+                ("border_volume", C.c_int32 * METRICS_MAX_PLANES), ("border_bit", C.c_int32 * METRICS_MAX_PLANES),
+                ("edt_plane", C.c_int32 * METRICS_MAX_PLANES), ("item_group", C.c_int32 * METRICS_MAX_PLANES),
+                ("tolerance", C.c_float * METRICS_MAX_PLANES), ("rank", (C.c_int64 * 2) * METRICS_MAX_PLANES),
                 ("borders", C.c_void_p), ("edt", C.c_void_p), ("out", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
@@ -720,6 +731,8 @@ class SegmLib:
         sig("segm_edt_sq", [C.POINTER(EdtSqArgs)], C.c_int)
         sig("segm_border_distances", [C.POINTER(BorderDistancesArgs)], C.c_int)
         sig("segm_border_distances_workspace_bytes", [C.c_int64, C.c_int32], C.c_size_t)
+        sig("segm_border_stats", [C.POINTER(BorderStatsArgs)], C.c_int)
+        sig("segm_border_stats_workspace_bytes", [C.c_int64, C.c_int32], C.c_size_t)
         sig("segm_edt_sq_long", [C.POINTER(EdtSqLongArgs)], C.c_int)
         sig("segm_edt_sq_long_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_planes_bbox", [C.POINTER(PlanesBboxArgs)], C.c_int)

@@ -11,12 +11,18 @@ both border volumes are cropped to it, and the crop is transformed by the brute-
 the linear-time one (csrc/edt_long.hip, sides up to 2048).  The crop is exact: every border voxel of either mask lies inside the
 box, so the nearest one does too.  `SEGM_EDT_LONG=1` (read per call) forces the box route and the linear-time kernel at every
 size, `SEGM_EDT_LONG=box` the box route with the kernel chosen by the crop's size, i.e. what a large volume gets.
+
+The evaluation report (`asd`, `assd`, `nsd`, `confusion` and the functions and `ALL_METRICS` of the reference's
+`light_training/evaluation/metric.py`, `case_report`, `evaluate_report`) needs no distance list: `_Pass.summary` asks
+`segm_border_stats` (csrc/surface_stats.hip) for counts, sums, maxima, within-tolerance counts and two exact order statistics per
+region, on the same distance-transform planes.  `hd95`, `hd`, `surface_distances`, `case_metrics` and `evaluate` keep the list route.
 """
 from __future__ import annotations
 
 import math
 import os
-from typing import Iterable, Optional, Sequence, Tuple
+from collections import namedtuple
+from typing import Dict, Iterable, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -147,6 +153,10 @@ def distance_transform_edt(mask, sampling: Optional[Sequence[float]] = None) -> 
     return e.sqrt()
 
 
+# per region: HD95 and HD of the joined list, the mean distance P -> G and G -> P, the voxel-counted surface Dice (`_Pass.summary`)
+SurfaceSummary = namedtuple("SurfaceSummary", "hd95 hd asd_pg asd_gp nsd")
+
+
 class _Pass:
     """region counts and borders of one (prediction, ground truth) pair, and the border-to-border distance lists made from them"""
 
@@ -227,6 +237,49 @@ class _Pass:
         else:
             vals = torch.stack(picks).double().cpu().numpy()              # second readback
         return [(float(v[0] + (v[1] - v[0]) * f), float(v[2])) for v, f in zip(vals, frac)]
+
+    def summary(self, regions_idx, spacing, tolerance=None):
+        """-> [SurfaceSummary] per region of `regions_idx` (each non-empty on both sides), with one readback for all of them: what
+        asd / assd / hd / hd95 and the surface Dice are made of, from segm_border_stats - the distance transform of `distances`, then
+        counts, sums, maxima and two order statistics instead of the distance lists and their sorts.  One group per region: the
+        P -> G item and the G -> P item; the ranks are `hausdorff`'s, from the border counts of the first readback."""
+        if not regions_idx:
+            return []
+        tol = -1.0 if tolerance is None else float(tolerance)
+        ranks, frac = [], []
+        for r in regions_idx:
+            n = self.counts[3][r] + self.counts[4][r]
+            rank = 0.95 * (n - 1)                                         # numpy.percentile, linear interpolation
+            lo = int(math.floor(rank))
+            ranks.append((lo, min(lo + 1, n - 1)))
+            frac.append(rank - lo)
+        w = L.METRICS_MAX_PLANES
+        if self.boxed:
+            outs = []
+            for k, r in enumerate(regions_idx):
+                z0, z1, y0, y1, x0, x1 = self.boxes[r]
+                crop = self.borders[:, z0:z1, y0:y1, x0:x1].contiguous()
+                edt = _edt_sq(self.lib, crop, [(0, r), (1, r)], spacing, self.mode)      # plane 0: to the border of P; 1: of G
+                outs.append(ops_raw.border_stats(self.lib, crop, edt, [(0, r, 1), (1, r, 0)], [0, 0], 1, [tol, tol], [ranks[k]]))
+            vals = _readback(outs[0] if len(outs) == 1 else torch.cat(outs))             # second readback
+            rows = [(vals[6 * w * k:6 * w * k + 4], vals[6 * w * k + 4:6 * w * k + 8], vals[6 * w * k + 4 * w:6 * w * k + 4 * w + 2])
+                    for k in range(len(regions_idx))]
+        else:
+            planes, items, groups = [], [], []
+            for i, r in enumerate(regions_idx):
+                planes += [(0, r), (1, r)]                                # edt plane 2 i: to the border of P; 2 i + 1: to the border of G
+                items += [(0, r, 2 * i + 1), (1, r, 2 * i)]
+                groups += [i, i]
+            edt = ops_raw.edt_sq(self.lib, self.borders, planes, spacing)
+            vals = _readback(ops_raw.border_stats(self.lib, self.borders, edt, items, groups, len(regions_idx), [tol] * len(items), ranks))
+            rows = [(vals[8 * i:8 * i + 4], vals[8 * i + 4:8 * i + 8], vals[4 * w + 2 * i:4 * w + 2 * i + 2]) for i in range(len(regions_idx))]
+        out = []
+        for (p, g, v), f in zip(rows, frac):
+            n_p, n_g = int(p[0]), int(g[0])
+            out.append(SurfaceSummary(hd95=float(v[0] + (v[1] - v[0]) * f), hd=float(max(p[2], g[2])),
+                                      asd_pg=p[1] / n_p, asd_gp=g[1] / n_g,
+                                      nsd=(p[3] + g[3]) / float(n_p + n_g) if tolerance is not None else math.nan))
+        return out
 
 
 def _binary_pass(result, reference, what) -> _Pass:
@@ -311,3 +364,202 @@ def evaluate(cases: Iterable, regions: Sequence[Sequence[int]] = BRATS_REGIONS, 
     if not rows:
         return results, np.full((len(regions), 2), np.nan), np.full((len(regions), 2), np.nan)
     return results, results.mean(axis=0), results.std(axis=0)
+
+
+# ---- the evaluation report: medpy's asd / assd, the surface Dice, and the metric table of light_training/evaluation/metric.py ------------
+def _binary_summary(result, reference, voxelspacing, tolerance, what) -> SurfaceSummary:
+    return _binary_pass(result, reference, what).summary([0], voxelspacing, tolerance)[0]
+
+
+def asd(result, reference, voxelspacing: Optional[Sequence[float]] = None) -> float:
+    """Average surface distance: the mean of `surface_distances(result, reference)`, added in fp64 (medpy.metric.binary.asd,
+    connectivity 1).  Not symmetric.  Raises RuntimeError when either volume is empty, as medpy does."""
+    return _binary_summary(result, reference, voxelspacing, None, "asd").asd_pg
+
+
+def assd(result, reference, voxelspacing: Optional[Sequence[float]] = None) -> float:
+    """Average symmetric surface distance: the mean of asd(result, reference) and asd(reference, result) (medpy.metric.binary.assd)"""
+    s = _binary_summary(result, reference, voxelspacing, None, "assd")
+    return (s.asd_pg + s.asd_gp) / 2.0
+
+
+def nsd(result, reference, tolerance: float, voxelspacing: Optional[Sequence[float]] = None) -> float:
+    """Surface Dice at `tolerance`, VOXEL-COUNTED: the number of border voxels of `result` within `tolerance` of the border of
+    `reference`, plus the number of border voxels of `reference` within `tolerance` of the border of `result`, over the number of
+    border voxels of both.  Every border voxel weighs 1: this is not the surface-area-weighted form, which weighs a voxel by the
+    area of its surface patch under the spacing.  Raises RuntimeError when either volume is empty."""
+    if not float(tolerance) >= 0.0:
+        raise RuntimeError(f"nsd: a tolerance >= 0 is required, got {tolerance}")
+    return _binary_summary(result, reference, voxelspacing, tolerance, "nsd").nsd
+
+
+_Confusion = namedtuple("_Confusion", "tp fp tn fn")
+
+
+def _confusion(n_p: int, n_g: int, both: int, voxels: int) -> _Confusion:
+    return _Confusion(both, n_p - both, voxels - n_p - n_g + both, n_g - both)
+
+
+def _none(nan: bool) -> float:
+    return math.nan if nan else 0.0
+
+
+# the four existence flags of the reference's ConfusionMatrix, from counts: empty = no voxel set, full = every voxel set
+def _test_empty(c): return c.tp + c.fp == 0
+def _test_full(c): return c.tn + c.fn == 0
+def _ref_empty(c): return c.tp + c.fn == 0
+def _ref_full(c): return c.tn + c.fp == 0
+
+
+def _m_dice(c, nan): return _none(nan) if _test_empty(c) and _ref_empty(c) else float(2.0 * c.tp / (2 * c.tp + c.fp + c.fn))
+def _m_jaccard(c, nan): return _none(nan) if _test_empty(c) and _ref_empty(c) else float(c.tp / (c.tp + c.fp + c.fn))
+def _m_precision(c, nan): return _none(nan) if _test_empty(c) else float(c.tp / (c.tp + c.fp))
+def _m_recall(c, nan): return _none(nan) if _ref_empty(c) else float(c.tp / (c.tp + c.fn))
+def _m_specificity(c, nan): return _none(nan) if _ref_full(c) else float(c.tn / (c.tn + c.fp))
+def _m_accuracy(c, nan): return float((c.tp + c.tn) / (c.tp + c.fp + c.tn + c.fn))
+def _m_for(c, nan): return _none(nan) if _test_full(c) else float(c.fn / (c.fn + c.tn))
+
+
+def _m_fscore(c, nan, beta=1.0):
+    p, r = _m_precision(c, nan), _m_recall(c, nan)
+    den = (beta * beta * p) + r
+    return math.nan if den == 0.0 else (1 + beta * beta) * p * r / den          # no true positive: NaN where the reference divides by zero
+
+
+_COUNT_METRICS = {
+    "False Positive Rate": lambda c, nan: 1 - _m_specificity(c, nan),
+    "Dice": _m_dice,
+    "Jaccard": _m_jaccard,
+    "Precision": _m_precision,
+    "Recall": _m_recall,
+    "Accuracy": _m_accuracy,
+    "False Omission Rate": _m_for,
+    "Negative Predictive Value": lambda c, nan: 1 - _m_for(c, nan),
+    "False Negative Rate": lambda c, nan: 1 - _m_recall(c, nan),
+    "True Negative Rate": _m_specificity,
+    "False Discovery Rate": lambda c, nan: 1 - _m_precision(c, nan),
+    "Total Positives Test": lambda c, nan: c.tp + c.fp,
+    "Total Negatives Test": lambda c, nan: c.tn + c.fn,
+    "Total Positives Reference": lambda c, nan: c.tp + c.fn,
+    "total Negatives Reference": lambda c, nan: c.tn + c.fp,
+}
+_SURFACE_METRICS = {
+    "Hausdorff Distance": lambda s: s.hd,
+    "Hausdorff Distance 95": lambda s: s.hd95,
+    "Avg. Symmetric Surface Distance": lambda s: (s.asd_pg + s.asd_gp) / 2.0,
+    "Avg. Surface Distance": lambda s: s.asd_pg,
+    "Surface Dice": lambda s: s.nsd,
+}
+
+
+def case_report(pred_labels, gt_labels, voxelspacing: Optional[Sequence[float]] = (1, 1, 1),
+                regions: Sequence[Sequence[int]] = BRATS_REGIONS, metrics: Optional[Sequence[str]] = None, tolerance: float = 1.0,
+                nan_for_nonexisting: bool = True) -> Dict[str, np.ndarray]:
+    """The metric table of light_training/evaluation/metric.py per region of two label volumes: {name: float64 (n_regions,)} for the
+    names of `metrics` (default: all of `ALL_METRICS`, i.e. the reference's 19 and "Surface Dice", the voxel-counted `nsd` at
+    `tolerance`).  The count entries follow the reference's formulas and `nan_for_nonexisting` rules on tp / fp / tn / fn.  The four
+    surface entries and "Surface Dice" are NaN (0 with nan_for_nonexisting=False) for a region whose prediction or ground truth is
+    empty or fills the volume; elsewhere "Hausdorff Distance 95" and "Dice" equal `case_metrics` bit for bit.  Any number of regions,
+    eight per kernel call; when `metrics` names no surface entry only the region pass runs."""
+    names = list(ALL_METRICS) if metrics is None else [str(m) for m in metrics]
+    unknown = [m for m in names if m not in ALL_METRICS]
+    if unknown:
+        raise RuntimeError(f"case_report: unknown metrics {unknown}; the names are {list(ALL_METRICS)}")
+    if not float(tolerance) >= 0.0:
+        raise RuntimeError(f"case_report: a tolerance >= 0 is required, got {tolerance}")
+    pred, gt = _pair(pred_labels, gt_labels, _labels, "case_report")
+    if len(regions) > L.METRICS_MAX_REGIONS:                              # eight at a time, concatenated
+        parts = [case_report(pred, gt, voxelspacing, g, names, tolerance, nan_for_nonexisting) for g in _groups(regions)]
+        return {m: np.concatenate([p[m] for p in parts]) for m in names}
+    n = len(regions)
+    surface = [m for m in names if m in _SURFACE_METRICS]
+    if surface:
+        p = _Pass(pred, gt, regions)
+        counts = p.counts
+    else:
+        _, c = ops_raw.seg_regions(L.get_lib(), pred, gt, _table(regions, pred.device))
+        counts = c[:, :n].tolist()
+    cms = [_confusion(counts[0][r], counts[1][r], counts[2][r], pred.numel()) for r in range(n)]
+    out = {m: np.full(n, _none(nan_for_nonexisting), dtype=np.float64) for m in names}
+    for m in names:
+        if m in _COUNT_METRICS:
+            out[m][:] = [_COUNT_METRICS[m](c, nan_for_nonexisting) for c in cms]
+    if surface:
+        live = [r for r, c in enumerate(cms) if not (_test_empty(c) or _test_full(c) or _ref_empty(c) or _ref_full(c))]
+        for r, s in zip(live, p.summary(live, voxelspacing, tolerance)):
+            for m in surface:
+                out[m][r] = _SURFACE_METRICS[m](s)
+    return out
+
+
+def confusion(pred, gt) -> Tuple[int, int, int, int]:
+    """(tp, fp, tn, fn) of two binary volumes (non-zero = inside), from the counts of one region pass"""
+    a, b = _pair(pred, gt, _mask, "confusion")
+    _, counts = ops_raw.seg_regions(L.get_lib(), a, b, _table(_BINARY, a.device))
+    c = counts[:, 0].tolist()
+    return tuple(_confusion(c[0], c[1], c[2], a.numel()))
+
+
+def _binary_metric(name):
+    count = name in _COUNT_METRICS
+
+    def fn(test, reference, nan_for_nonexisting: bool = True, voxel_spacing: Optional[Sequence[float]] = None, tolerance: float = 1.0):
+        a, b = _pair(test, reference, _mask, name)
+        v = case_report(a, b, voxel_spacing, _BINARY, [name], tolerance, nan_for_nonexisting)[name][0]
+        return int(v) if name.lower().startswith("total") else float(v)
+    fn.__doc__ = (f'"{name}" of two binary volumes as light_training/evaluation/metric.py defines it'
+                  + (" (counts only)" if count else " (connectivity 1; NaN, or 0, when either volume is empty or full)"))
+    return fn
+
+
+ALL_METRICS = {name: _binary_metric(name) for name in (
+    "False Positive Rate", "Dice", "Jaccard", "Hausdorff Distance", "Hausdorff Distance 95", "Precision", "Recall",
+    "Avg. Symmetric Surface Distance", "Avg. Surface Distance", "Accuracy", "False Omission Rate", "Negative Predictive Value",
+    "False Negative Rate", "True Negative Rate", "False Discovery Rate", "Total Positives Test", "Total Negatives Test",
+    "Total Positives Reference", "total Negatives Reference", "Surface Dice")}
+
+# one function per name of the reference's module
+false_positive_rate = ALL_METRICS["False Positive Rate"]
+dice = ALL_METRICS["Dice"]
+jaccard = ALL_METRICS["Jaccard"]
+hausdorff_distance = ALL_METRICS["Hausdorff Distance"]
+hausdorff_distance_95 = ALL_METRICS["Hausdorff Distance 95"]
+precision = ALL_METRICS["Precision"]
+recall = sensitivity = ALL_METRICS["Recall"]
+avg_surface_distance_symmetric = ALL_METRICS["Avg. Symmetric Surface Distance"]
+avg_surface_distance = ALL_METRICS["Avg. Surface Distance"]
+accuracy = ALL_METRICS["Accuracy"]
+false_omission_rate = ALL_METRICS["False Omission Rate"]
+negative_predictive_value = ALL_METRICS["Negative Predictive Value"]
+false_negative_rate = ALL_METRICS["False Negative Rate"]
+true_negative_rate = specificity = ALL_METRICS["True Negative Rate"]
+false_discovery_rate = ALL_METRICS["False Discovery Rate"]
+total_positives_test = ALL_METRICS["Total Positives Test"]
+total_negatives_test = ALL_METRICS["Total Negatives Test"]
+total_positives_reference = ALL_METRICS["Total Positives Reference"]
+total_negatives_reference = ALL_METRICS["total Negatives Reference"]
+surface_dice = ALL_METRICS["Surface Dice"]
+
+
+def fscore(test, reference, nan_for_nonexisting: bool = True, beta: float = 1.0) -> float:
+    """(1 + b^2) precision recall / (b^2 precision + recall); NaN where that is 0 / 0 (no true positive)"""
+    return _m_fscore(_Confusion(*confusion(test, reference)), nan_for_nonexisting, float(beta))
+
+
+def evaluate_report(cases: Iterable, regions: Sequence[Sequence[int]] = BRATS_REGIONS, metrics: Optional[Sequence[str]] = None,
+                    tolerance: float = 1.0, nan_for_nonexisting: bool = True):
+    """cases: an iterable of (pred_labels, gt_labels) or (pred_labels, gt_labels, voxelspacing).  -> ({name: (n_cases, n_regions)},
+    {name: (n_regions,)}): `case_report` per case, and per region the mean over the cases that have a value (numpy.nanmean; NaN
+    where no case has one)."""
+    names = list(ALL_METRICS) if metrics is None else [str(m) for m in metrics]
+    rows = []
+    for case in cases:
+        spacing = case[2] if len(case) > 2 else (1, 1, 1)
+        rows.append(case_report(case[0], case[1], spacing, regions, names, tolerance, nan_for_nonexisting))
+    per_case = {m: np.stack([r[m] for r in rows]) if rows else np.zeros((0, len(regions))) for m in names}
+    mean = {}
+    for m, a in per_case.items():
+        have = ~np.isnan(a)
+        cnt = have.sum(axis=0)
+        mean[m] = np.where(cnt > 0, np.where(have, a, 0.0).sum(axis=0) / np.maximum(cnt, 1), np.nan)
+    return per_case, mean

@@ -1929,6 +1929,49 @@ def border_distances(lib: L.SegmLib, borders: torch.Tensor, edt: torch.Tensor, i
     return out
 
 
+def border_stats(lib: L.SegmLib, borders: torch.Tensor, edt: torch.Tensor, items, groups, n_groups: int, tolerances=None,
+                 ranks=None) -> torch.Tensor:
+    """What the surface metrics need of `border_distances`' lists, without the lists (segm_border_stats).  borders, edt and items
+    as in `border_distances`; groups: the group of each item (the items of a group form one joined list); tolerances: one per item
+    (None or a negative value: count nothing); ranks: per group two 0-based ranks in the ascending joined list (a negative one: none).
+    -> (96,) fp64 on the device: [4 i ..] = count, sum, max and within-tolerance count of item i; [64 + 2 g ..] = the two order
+    statistics of group g, NaN for a rank outside the list."""
+    _label_volume(borders, "border_stats: borders", dims=(4,))
+    if not isinstance(edt, torch.Tensor) or edt.dtype not in (torch.int32, torch.float32) or edt.dim() != 4 or not edt.is_contiguous():
+        raise RuntimeError("border_stats: edt must be a contiguous (P, D, H, W) int32 or fp32 tensor")
+    if edt.shape[1:] != borders.shape[1:] or edt.device != borders.device:
+        raise RuntimeError(f"border_stats: borders {tuple(borders.shape)} and edt {tuple(edt.shape)} must share volume shape and device")
+    items = [(int(v), int(b), int(p)) for v, b, p in items]
+    _plane_list([(v, b) for v, b, _ in items], borders.shape[0], "border_stats")
+    groups = [int(g) for g in groups]
+    n_groups = int(n_groups)
+    if not 1 <= n_groups <= L.METRICS_MAX_PLANES:
+        raise RuntimeError(f"border_stats: between 1 and {L.METRICS_MAX_PLANES} groups per call, got {n_groups}")
+    if len(groups) != len(items) or any(not 0 <= g < n_groups for g in groups) or any(not 0 <= p < edt.shape[0] for _, _, p in items):
+        raise RuntimeError("border_stats: one group in [0, n_groups) per item and edt planes inside `edt` are required")
+    tolerances = [-1.0] * len(items) if tolerances is None else [-1.0 if t is None else float(t) for t in tolerances]
+    ranks = [(-1, -1)] * n_groups if ranks is None else [(int(a), int(b)) for a, b in ranks]
+    if len(tolerances) != len(items) or len(ranks) != n_groups:
+        raise RuntimeError("border_stats: one tolerance per item and one pair of ranks per group are required")
+    N = borders[0].numel()
+    if max(groups.count(g) for g in range(n_groups)) * N >= 1 << 32:
+        raise RuntimeError("border_stats: a group's items times the voxels must stay below 2^32")
+    out = torch.empty(6 * L.METRICS_MAX_PLANES, dtype=torch.float64, device=borders.device)
+    nbytes = lib.dll.segm_border_stats_workspace_bytes(N, len(items))
+    ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=borders.device)
+    a = L.BorderStatsArgs()
+    a.voxels, a.n_volumes, a.n_planes, a.n_items, a.n_groups = N, borders.shape[0], edt.shape[0], len(items), n_groups
+    a.fp32 = int(edt.dtype == torch.float32)
+    for i, ((v, b, p), g, t) in enumerate(zip(items, groups, tolerances)):
+        a.border_volume[i], a.border_bit[i], a.edt_plane[i], a.item_group[i], a.tolerance[i] = v, b, p, g, t
+    for g, (lo, hi) in enumerate(ranks):
+        a.rank[g][0], a.rank[g][1] = lo, hi
+    a.borders, a.edt, a.out = borders.data_ptr(), edt.data_ptr(), out.data_ptr()
+    a.workspace, a.workspace_bytes, a.stream = ws.data_ptr(), ws.numel() * 8, L.stream_handle(borders)
+    lib.check(lib.dll.segm_border_stats(a), "border_stats")
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------
 # finishing a prediction (csrc/postprocess.hip): logits -> labels, connected components, sizes, selection
 # ---------------------------------------------------------------------------------------------------------
@@ -2870,7 +2913,7 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "instnorm_bwd", "instnorm_tail_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
-              "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
+              "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "border_stats", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
               "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "spline_coefs", "affine_spline3", "affine_labels",
               "zoom_nearest", "gauss_blur", "intensity_stats", "intensity_apply", "window_gather", "window_count", "window_blend",
               "window_finish"):

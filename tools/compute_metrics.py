@@ -2,8 +2,12 @@
 form of the reference's 5_compute_metrics.py.
 
     python tools/compute_metrics.py --pred DIR --gt DIR [--out FILE.npy] [--spacing Z Y X] [--labels 1,2,...]
+                                    [--report FILE.json [--tolerance T]]
 
 --labels scores one region per listed label (e.g. the nine organs of a CT label map) instead of the BraTS regions; any number of them.
+--report also writes the metric table of the reference's light_training/evaluation/metric.py (its 19 entries and the voxel-counted
+"Surface Dice" at --tolerance, default 1.0; segmamba_amd.metrics.case_report) per case and on average over the cases that have a
+value, as JSON: {"regions", "tolerance", "cases": {name: {metric: [per region]}}, "mean": {metric: [per region]}}, null for NaN.
 
 Cases are the files of --pred that have a file of the same name in --gt.  Label volumes are read from .npy and .npz (the first
 array, or the one called "labels" / "seg" / "arr_0"); .nii / .nii.gz through nibabel or SimpleITK where one is installed, else through
@@ -64,6 +68,8 @@ def main(argv=None):
     ap.add_argument("--out")
     ap.add_argument("--spacing", type=float, nargs=3, default=(1.0, 1.0, 1.0), metavar=("Z", "Y", "X"))
     ap.add_argument("--labels", default=None, help="comma-separated labels: one region per label instead of the BraTS regions")
+    ap.add_argument("--report", default=None, metavar="FILE.json", help="also write the full metric table per case and on average")
+    ap.add_argument("--tolerance", type=float, default=1.0, help="the tolerance of the report's Surface Dice, in the unit of --spacing")
     args = ap.parse_args(argv)
     from segmamba_amd import metrics
     regions = metrics.BRATS_REGIONS
@@ -85,6 +91,18 @@ def main(argv=None):
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         np.save(args.out, results)
+    if args.report:
+        import json
+        per_case, mean = metrics.evaluate_report(cases(), regions, tolerance=args.tolerance)
+
+        def plain(a):
+            return [None if np.isnan(v) else float(v) for v in a]
+        rec = {"regions": [list(r) for r in regions], "tolerance": args.tolerance, "spacing": list(args.spacing),
+               "cases": {n: {m: plain(a[i]) for m, a in per_case.items()} for i, n in enumerate(names)},
+               "mean": {m: plain(a) for m, a in mean.items()}}
+        os.makedirs(os.path.dirname(os.path.abspath(args.report)), exist_ok=True)
+        with open(args.report, "w") as f:
+            json.dump(rec, f, indent=1)
     return results
 
 
