@@ -1083,7 +1083,8 @@ typedef struct segm_resample_argmax_args {
 } segm_resample_argmax_args;
 int segm_resample_argmax(const segm_resample_argmax_args* args);
 
-/* Connected components at connectivity 1 (six face neighbours; the outside of the volume connects nothing).
+/* Connected components at connectivity 1 (six face neighbours; the outside of the volume connects nothing).  Connectivity 2 and 3:
+ * segm_ccl_roots_conn below.
  * A voxel is inside the mask iff ((bit >= 0 ? (v >> bit) & 1 : v != 0) != invert), v its byte of `volume`.
  *   roots[i] = -1 outside the mask, otherwise the SMALLEST linear index (z * height + y) * width + x of the voxel's component
  * - a definition that does not depend on the order in which anything happened: two calls are bit-equal.
@@ -1172,6 +1173,40 @@ typedef struct segm_ccl_label_select_args {
 } segm_ccl_label_select_args;
 size_t segm_ccl_label_select_workspace_bytes(int64_t voxels);
 int segm_ccl_label_select(const segm_ccl_label_select_args* args);
+
+/* Connected components at connectivity 1, 2 or 3 (additive to ABI 10; csrc/ccl_conn.hip).  `connectivity` c is that of
+ * scipy.ndimage.generate_binary_structure(3, c) and skimage.measure.label(connectivity=c): two voxels are neighbours when their
+ * offset has at most c non-zero coordinates, each of them +-1 - 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners)
+ * neighbours.  nnU-Net's post-processing, cc3d and the BraTS lesion-wise tooling label at full connectivity (3); the reference's
+ * large_connected_domain at 1.  The outside of the volume connects nothing: a row's last voxel is no neighbour of the next row's first.
+ * Everything else is the contract of segm_ccl_roots: the mask by `bit` / `invert`, roots[i] = -1 outside the mask, otherwise the
+ * SMALLEST linear index of the voxel's component (independent of any order: two calls are bit-equal), three launches, no readback,
+ * a workspace of segm_ccl_roots_workspace_bytes.  The roots go to segm_ccl_sizes / segm_ccl_select unchanged.
+ * connectivity == 1 makes the launches of segm_ccl_roots.  Any other value than 1, 2, 3 is SEGM_E_SHAPE.  Every refusal launches
+ * nothing and leaves `roots` untouched. */
+typedef struct segm_ccl_roots_conn_args {
+    int32_t depth, height, width;
+    int32_t bit;                   /* 0 .. 7, or -1: value != 0 */
+    int32_t invert, connectivity;  /* 1, 2, 3 */
+    const uint8_t* volume;
+    int32_t* roots;                /* (depth, height, width) */
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_ccl_roots_conn_args;
+int segm_ccl_roots_conn(const segm_ccl_roots_conn_args* args);
+
+/* The labelled form: two voxels are one component when a path of c-neighbours with the SAME NON-ZERO label joins them (two different
+ * labels that touch, diagonally or not, are never joined).  The contract of segm_ccl_label_roots otherwise: on `labels == k` the
+ * roots equal segm_ccl_roots_conn of that mask at the same connectivity; workspace of segm_ccl_label_roots_workspace_bytes;
+ * connectivity == 1 makes the launches of segm_ccl_label_roots.  segm_ccl_sizes and segm_ccl_label_select take the roots unchanged. */
+typedef struct segm_ccl_label_roots_conn_args {
+    int32_t depth, height, width, connectivity;
+    const uint8_t* labels;         /* (depth, height, width) */
+    int32_t* roots;                /* (depth, height, width) */
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_ccl_label_roots_conn_args;
+int segm_ccl_label_roots_conn(const segm_ccl_label_roots_conn_args* args);
 
 /* ------------------------------------------------------------------------------------------------
  * Preparing a case on the device (additive to ABI 10; csrc/preprocess.hip).

@@ -153,15 +153,7 @@ static void launch_resample(const ResDev& P, bool ident, hipStream_t st) {
 }
 
 // ---- connected components -----------------------------------------------------------------------------------------------------------
-struct CclDev {
-    const uint8_t* vol;
-    int32_t* lab;
-    int32_t* roots;
-    int32_t D, H, W, N;
-    int32_t bit, invert;
-    int32_t tx, ty;                     // tiles along x and y
-};
-
+// struct CclDev: ccl_common.h (ccl_conn.hip launches ccl_flatten_kernel with it)
 __device__ __forceinline__ bool ccl_inside(uint32_t v, int bit, int invert) {
     const int in = bit >= 0 ? (int)((v >> bit) & 1u) : (int)(v != 0u);
     return in != invert;

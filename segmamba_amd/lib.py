@@ -335,6 +335,7 @@ EXPORTS = (
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
     "segm_ccl_label_roots", "segm_ccl_label_roots_workspace_bytes", "segm_ccl_label_select", "segm_ccl_label_select_workspace_bytes",
+    "segm_ccl_roots_conn", "segm_ccl_label_roots_conn",
     "segm_nonzero_mask_bbox", "segm_crop_stats", "segm_crop_stats_workspace_bytes", "segm_crop_normalize",
     "segm_crop_clip_normalize", "segm_fg_workspace_bytes", "segm_fg_count", "segm_fg_order_stats", "segm_fg_gather",
     "segm_cross_entropy_map", "segm_cross_entropy_map_bwd", "segm_topk_select", "segm_topk_select_workspace_bytes",
@@ -453,6 +454,19 @@ class CclSelectArgs(C.Structure):
 
 class CclLabelRootsArgs(C.Structure):
     _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("reserved", C.c_int32),
+                ("labels", C.c_void_p), ("roots", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class CclRootsConnArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("bit", C.c_int32),
+                ("invert", C.c_int32), ("connectivity", C.c_int32),
+                ("volume", C.c_void_p), ("roots", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("stream", C.c_void_p)]
+
+
+class CclLabelRootsConnArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32), ("connectivity", C.c_int32),
                 ("labels", C.c_void_p), ("roots", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
                 ("stream", C.c_void_p)]
 
@@ -746,6 +760,8 @@ class SegmLib:
         sig("segm_ccl_label_roots_workspace_bytes", [C.c_int64], C.c_size_t)
         sig("segm_ccl_label_select", [C.POINTER(CclLabelSelectArgs)], C.c_int)
         sig("segm_ccl_label_select_workspace_bytes", [C.c_int64], C.c_size_t)
+        sig("segm_ccl_roots_conn", [C.POINTER(CclRootsConnArgs)], C.c_int)
+        sig("segm_ccl_label_roots_conn", [C.POINTER(CclLabelRootsConnArgs)], C.c_int)
         sig("segm_nonzero_mask_bbox", [C.POINTER(NonzeroMaskBboxArgs)], C.c_int)
         sig("segm_crop_stats", [C.POINTER(CropArgs)], C.c_int)
         sig("segm_crop_stats_workspace_bytes", [C.c_int32] * 4, C.c_size_t)

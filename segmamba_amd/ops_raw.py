@@ -2049,9 +2049,19 @@ def resample_argmax(lib: L.SegmLib, logits: torch.Tensor, out_shape=None, box_st
     return out if regions is None else (out, regions)
 
 
-def ccl_roots(lib: L.SegmLib, volume: torch.Tensor, bit: int = -1, invert: bool = False, out: torch.Tensor = None) -> torch.Tensor:
-    """Connected components at connectivity 1 of the mask `(volume >> bit) & 1` (bit = -1: `volume != 0`), or of its complement with
-    `invert`.  volume (D, H, W) uint8.  -> int32 (D, H, W): -1 outside the mask, else the smallest linear index of the voxel's component."""
+def _connectivity(connectivity, what: str) -> int:
+    """1, 2 or 3 as in scipy.ndimage.generate_binary_structure(3, c): 6, 18 or 26 neighbours"""
+    if isinstance(connectivity, bool) or connectivity not in (1, 2, 3):
+        raise ValueError(f"{what}: connectivity must be 1, 2 or 3, got {connectivity!r}")
+    return int(connectivity)
+
+
+def ccl_roots(lib: L.SegmLib, volume: torch.Tensor, bit: int = -1, invert: bool = False, out: torch.Tensor = None,
+              connectivity: int = 1) -> torch.Tensor:
+    """Connected components of the mask `(volume >> bit) & 1` (bit = -1: `volume != 0`), or of its complement with `invert`, at
+    `connectivity` 1, 2 or 3 (6, 18 or 26 neighbours; 1 calls segm_ccl_roots, 2 and 3 segm_ccl_roots_conn).  volume (D, H, W) uint8.
+    -> int32 (D, H, W): -1 outside the mask, else the smallest linear index of the voxel's component."""
+    connectivity = _connectivity(connectivity, "ccl_roots")
     _ccl_volume(volume, "ccl_roots: volume")
     bit = int(bit)
     if not -1 <= bit <= 7:
@@ -2062,11 +2072,15 @@ def ccl_roots(lib: L.SegmLib, volume: torch.Tensor, bit: int = -1, invert: bool 
         _same_volume(out, "ccl_roots: out", torch.int32, volume.shape, volume.device)
     nbytes = lib.dll.segm_ccl_roots_workspace_bytes(volume.numel())
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=volume.device)
-    a = L.CclRootsArgs()
+    a = L.CclRootsArgs() if connectivity == 1 else L.CclRootsConnArgs()
     a.depth, a.height, a.width = volume.shape
     a.bit, a.invert = bit, 1 if invert else 0
     a.volume, a.roots, a.workspace, a.workspace_bytes, a.stream = volume.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(volume)
-    lib.check(lib.dll.segm_ccl_roots(a), "ccl_roots")
+    if connectivity == 1:
+        lib.check(lib.dll.segm_ccl_roots(a), "ccl_roots")
+    else:
+        a.connectivity = connectivity
+        lib.check(lib.dll.segm_ccl_roots_conn(a), "ccl_roots")
     return out
 
 
@@ -2114,10 +2128,12 @@ def ccl_select(lib: L.SegmLib, roots: torch.Tensor, sizes: torch.Tensor, mode: i
     return out, info
 
 
-def ccl_label_roots(lib: L.SegmLib, labels: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-    """Connected components at connectivity 1 of every class of a label volume in one pass: two voxels are joined by face neighbours
-    of the same non-zero label.  labels (D, H, W) uint8.  -> int32 (D, H, W): -1 where the label is 0, else the smallest linear index
-    of the voxel's component (on `labels == c` what `ccl_roots(labels == c)` gives)."""
+def ccl_label_roots(lib: L.SegmLib, labels: torch.Tensor, out: torch.Tensor = None, connectivity: int = 1) -> torch.Tensor:
+    """Connected components of every class of a label volume in one pass: two voxels are joined by a path of neighbours of the same
+    non-zero label, at `connectivity` 1, 2 or 3 (6, 18 or 26 neighbours; 1 calls segm_ccl_label_roots, 2 and 3
+    segm_ccl_label_roots_conn).  labels (D, H, W) uint8.  -> int32 (D, H, W): -1 where the label is 0, else the smallest linear index
+    of the voxel's component (on `labels == k` what `ccl_roots(labels == k)` gives at the same connectivity)."""
+    connectivity = _connectivity(connectivity, "ccl_label_roots")
     _ccl_volume(labels, "ccl_label_roots: labels")
     if out is None:
         out = torch.empty(labels.shape, dtype=torch.int32, device=labels.device)
@@ -2125,10 +2141,14 @@ def ccl_label_roots(lib: L.SegmLib, labels: torch.Tensor, out: torch.Tensor = No
         _same_volume(out, "ccl_label_roots: out", torch.int32, labels.shape, labels.device)
     nbytes = lib.dll.segm_ccl_label_roots_workspace_bytes(labels.numel())
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
-    a = L.CclLabelRootsArgs()
+    a = L.CclLabelRootsArgs() if connectivity == 1 else L.CclLabelRootsConnArgs()
     a.depth, a.height, a.width = labels.shape
     a.labels, a.roots, a.workspace, a.workspace_bytes, a.stream = labels.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(labels)
-    lib.check(lib.dll.segm_ccl_label_roots(a), "ccl_label_roots")
+    if connectivity == 1:
+        lib.check(lib.dll.segm_ccl_label_roots(a), "ccl_label_roots")
+    else:
+        a.connectivity = connectivity
+        lib.check(lib.dll.segm_ccl_label_roots_conn(a), "ccl_label_roots")
     return out
 
 

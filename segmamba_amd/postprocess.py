@@ -4,8 +4,17 @@ The stage of the reference's pipeline between `maybe_mirror_and_predict` and the
 light_training/prediction.py): resample the logits to the pre-resample crop shape, arg-max, paste into the un-cropped volume
 (`labels_from_logits`: one launch), and the optional `large_connected_domain` post-processing - label the components, keep the
 largest, fill its holes (`largest_connected_domain`).  The functions carry the reference's, scipy's and skimage's names and
-definitions at connectivity 1 (six face neighbours; the only connectivity here), for 3-D volumes of fewer than 2^31 voxels.
-Tensors stay on the device; numpy arrays and host tensors are uploaded.  No call reads a volume back.
+definitions for 3-D volumes of fewer than 2^31 voxels.  Tensors stay on the device; numpy arrays and host tensors are uploaded.  No
+call reads a volume back.
+
+`connectivity` is 1, 2 or 3 as in `scipy.ndimage.generate_binary_structure(3, c)` and `skimage.measure.label(connectivity=c)`: 6
+(faces), 18 (faces and edges) or 26 (faces, edges and corners) neighbours.  The default everywhere is 1, which is what the reference's
+`large_connected_domain` passes; nnU-Net's post-processing, cc3d and the BraTS lesion-wise tooling label at 3 (csrc/ccl_conn.hip).
+It is the connectivity of the FOREGROUND components.  Where a function also fills holes (`largest_connected_domain`,
+`postprocess_labels`, `keep_largest_per_class(fill_holes=True)`) the background flood stays at connectivity 1 whatever the foreground's:
+that is `measure.label(connectivity=c)` followed by `ndimage.binary_fill_holes(...)` with its default structure, and the topologically
+consistent pairing (a 26-connected foreground with a 6-connected background).  Only `binary_fill_holes` takes the background's
+connectivity itself.  Any other value is a ValueError.
 
 Where this deliberately differs from the reference:
   * `largest_connected_domain` of an empty mask returns the empty mask (the reference raises IndexError on `volume_sort[-1]`);
@@ -41,15 +50,18 @@ def _mask(x, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def component_roots(mask) -> torch.Tensor:
-    """int32 (D, H, W): -1 outside the mask, otherwise the smallest linear index of the voxel's component"""
-    return ops_raw.ccl_roots(L.get_lib(), _mask(mask, "component_roots"))
+def component_roots(mask, connectivity: int = 1) -> torch.Tensor:
+    """int32 (D, H, W): -1 outside the mask, otherwise the smallest linear index of the voxel's component at `connectivity`"""
+    connectivity = ops_raw._connectivity(connectivity, "component_roots")
+    return ops_raw.ccl_roots(L.get_lib(), _mask(mask, "component_roots"), connectivity=connectivity)
 
 
-def label(mask, return_num: bool = True):
-    """scipy.ndimage.label / skimage.measure.label(connectivity=1): int32 labels, 0 = background, the components numbered 1 .. num in
-    memory order of their first voxel.  -> (labels, num) or labels."""
-    roots = ops_raw.ccl_roots(L.get_lib(), _mask(mask, "label"))
+def label(mask, return_num: bool = True, connectivity: int = 1):
+    """scipy.ndimage.label(structure=generate_binary_structure(3, connectivity)) / skimage.measure.label(connectivity=connectivity):
+    int32 labels, 0 = background, the components numbered 1 .. num in memory order of their first voxel (ascending root: scipy's
+    raster order at every connectivity).  -> (labels, num) or labels."""
+    connectivity = ops_raw._connectivity(connectivity, "label")
+    roots = ops_raw.ccl_roots(L.get_lib(), _mask(mask, "label"), connectivity=connectivity)
     flat = roots.reshape(-1)
     is_root = flat == torch.arange(flat.numel(), dtype=torch.int32, device=flat.device)
     rank = torch.cumsum(is_root, 0, dtype=torch.int32)                    # rank of a root among the roots = its number
@@ -58,42 +70,52 @@ def label(mask, return_num: bool = True):
     return (labels, int(rank[-1].item())) if return_num else labels
 
 
-def _fill(lib, m: torch.Tensor) -> torch.Tensor:
-    roots = ops_raw.ccl_roots(lib, m, invert=True)
+def _fill(lib, m: torch.Tensor, connectivity: int = 1) -> torch.Tensor:
+    """`connectivity` of the background flood"""
+    roots = ops_raw.ccl_roots(lib, m, invert=True, connectivity=connectivity)
     sizes, touches = ops_raw.ccl_sizes(lib, roots)
     return ops_raw.ccl_select(lib, roots, sizes, L.CCL_FILL, touches=touches)[0]
 
 
-def _keep(lib, m: torch.Tensor, keep, bit: int = -1) -> torch.Tensor:
-    roots = ops_raw.ccl_roots(lib, m, bit=bit)
+def _keep(lib, m: torch.Tensor, keep, bit: int = -1, connectivity: int = 1) -> torch.Tensor:
+    roots = ops_raw.ccl_roots(lib, m, bit=bit, connectivity=connectivity)
     sizes, _ = ops_raw.ccl_sizes(lib, roots)
     if keep == "largest":
         return ops_raw.ccl_select(lib, roots, sizes, L.CCL_LARGEST)[0]
     return ops_raw.ccl_select(lib, roots, sizes, L.CCL_MIN_SIZE, min_size=int(keep))[0]
 
 
-def binary_fill_holes(mask) -> torch.Tensor:
-    """scipy.ndimage.binary_fill_holes with the default structure: the mask plus every zero voxel that no path of face-adjacent zero
-    voxels connects to a face of the volume.  -> uint8 0 / 1."""
-    return _fill(L.get_lib(), _mask(mask, "binary_fill_holes"))
+def binary_fill_holes(mask, connectivity: int = 1) -> torch.Tensor:
+    """scipy.ndimage.binary_fill_holes: the mask plus every zero voxel that no path of neighbouring zero voxels connects to a face of
+    the volume.  `connectivity` is that of the BACKGROUND flood, scipy's `structure=generate_binary_structure(3, connectivity)`; the
+    default 1 (face-adjacent zero voxels) is scipy's default structure.  At 3 a hole that opens to the outside through a corner is no
+    hole.  -> uint8 0 / 1."""
+    connectivity = ops_raw._connectivity(connectivity, "binary_fill_holes")
+    return _fill(L.get_lib(), _mask(mask, "binary_fill_holes"), connectivity)
 
 
-def remove_small_components(mask, min_size: int) -> torch.Tensor:
-    """the voxels of the components of at least `min_size` voxels (skimage.morphology.remove_small_objects keeps size >= min_size)"""
-    return _keep(L.get_lib(), _mask(mask, "remove_small_components"), int(min_size))
+def remove_small_components(mask, min_size: int, connectivity: int = 1) -> torch.Tensor:
+    """the voxels of the components (at `connectivity`) of at least `min_size` voxels (skimage.morphology.remove_small_objects keeps
+    size >= min_size)"""
+    connectivity = ops_raw._connectivity(connectivity, "remove_small_components")
+    return _keep(L.get_lib(), _mask(mask, "remove_small_components"), int(min_size), connectivity=connectivity)
 
 
-def largest_connected_domain(mask) -> torch.Tensor:
+def largest_connected_domain(mask, connectivity: int = 1) -> torch.Tensor:
     """`large_connected_domain` of the reference (prediction.py:17-27): the largest component, its holes filled.  -> uint8 0 / 1.
-    An empty mask comes back empty; equal sizes: the component that comes last in memory order."""
+    An empty mask comes back empty; equal sizes: the component that comes last in memory order.  `connectivity` is that of the
+    components (the reference passes 1); the holes are filled at background connectivity 1 whatever it is, as
+    `measure.label(connectivity=c)` followed by `ndimage.binary_fill_holes(...)` does."""
+    connectivity = ops_raw._connectivity(connectivity, "largest_connected_domain")
     lib = L.get_lib()
-    return _fill(lib, _keep(lib, _mask(mask, "largest_connected_domain"), "largest"))
+    return _fill(lib, _keep(lib, _mask(mask, "largest_connected_domain"), "largest", connectivity=connectivity))
 
 
-def component_summary(mask) -> Tuple[int, int]:
-    """(number of components, voxels of the largest): two scalars read back"""
+def component_summary(mask, connectivity: int = 1) -> Tuple[int, int]:
+    """(number of components at `connectivity`, voxels of the largest): two scalars read back"""
+    connectivity = ops_raw._connectivity(connectivity, "component_summary")
     lib = L.get_lib()
-    roots = ops_raw.ccl_roots(lib, _mask(mask, "component_summary"))
+    roots = ops_raw.ccl_roots(lib, _mask(mask, "component_summary"), connectivity=connectivity)
     sizes, _ = ops_raw.ccl_sizes(lib, roots)
     info = ops_raw.ccl_select(lib, roots, sizes, L.CCL_LARGEST)[1].tolist()
     return int(info[0]), int(info[2])
@@ -131,10 +153,13 @@ def labels_from_logits(logits, properties: Optional[dict] = None, regions: Optio
                                    max_classes=L.RESAMPLE_CLASS_LIMIT)
 
 
-def postprocess_labels(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS, keep="largest", fill_holes: bool = True) -> torch.Tensor:
+def postprocess_labels(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS, keep="largest", fill_holes: bool = True,
+                       connectivity: int = 1) -> torch.Tensor:
     """The per-region form for a label map (this project's addition).  For every region in turn: its mask is reduced to the kept
-    components (`keep` = "largest" or a minimum voxel count) and, with `fill_holes`, filled; the region's voxels that fall outside
-    the result become 0.  Voxels are only ever removed: a filled hole keeps whatever label it had.  -> uint8 labels."""
+    components (`keep` = "largest" or a minimum voxel count; components at `connectivity`) and, with `fill_holes`, filled (at
+    background connectivity 1 whatever `connectivity` is); the region's voxels that fall outside the result become 0.  Voxels are
+    only ever removed: a filled hole keeps whatever label it had.  -> uint8 labels."""
+    connectivity = ops_raw._connectivity(connectivity, "postprocess_labels")
     t = _to_device(labels)
     if t.dim() != 3:
         raise RuntimeError(f"postprocess_labels: a (D, H, W) label volume is required, got shape {tuple(t.shape)}")
@@ -142,7 +167,7 @@ def postprocess_labels(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS,
     lib = L.get_lib()
     for r in range(len(regions)):
         bits = _table(regions, out.device)[out.long()].contiguous()
-        kept = _keep(lib, bits, keep, bit=r)
+        kept = _keep(lib, bits, keep, bit=r, connectivity=connectivity)
         if fill_holes:
             kept = _fill(lib, kept)
         inside = ((bits >> r) & 1).bool()
@@ -165,28 +190,33 @@ def _label_volume(x, what: str) -> torch.Tensor:
     return t.contiguous()
 
 
-def label_component_roots(labels) -> torch.Tensor:
+def label_component_roots(labels, connectivity: int = 1) -> torch.Tensor:
     """int32 (D, H, W): -1 where the label is 0, otherwise the smallest linear index of the voxel's component; a component is a set
-    of voxels of ONE non-zero label joined by face neighbours.  On `labels == c` this is `component_roots(labels == c)`."""
-    return ops_raw.ccl_label_roots(L.get_lib(), _label_volume(labels, "label_component_roots"))
+    of voxels of ONE non-zero label joined by neighbours at `connectivity`.  On `labels == k` this is
+    `component_roots(labels == k, connectivity)`."""
+    connectivity = ops_raw._connectivity(connectivity, "label_component_roots")
+    return ops_raw.ccl_label_roots(L.get_lib(), _label_volume(labels, "label_component_roots"), connectivity=connectivity)
 
 
-def _label_select(lib, t: torch.Tensor, keep, apply=None):
-    roots = ops_raw.ccl_label_roots(lib, t)
+def _label_select(lib, t: torch.Tensor, keep, apply=None, connectivity: int = 1):
+    roots = ops_raw.ccl_label_roots(lib, t, connectivity=connectivity)
     sizes, _ = ops_raw.ccl_sizes(lib, roots)
     if keep == "largest":
         return ops_raw.ccl_label_select(lib, t, roots, sizes, L.CCL_LARGEST, apply=apply)
     return ops_raw.ccl_label_select(lib, t, roots, sizes, L.CCL_MIN_SIZE, min_size=int(keep), apply=apply)
 
 
-def keep_largest_per_class(labels, classes: Optional[Sequence[int]] = None, keep="largest", fill_holes: bool = False) -> torch.Tensor:
+def keep_largest_per_class(labels, classes: Optional[Sequence[int]] = None, keep="largest", fill_holes: bool = False,
+                           connectivity: int = 1) -> torch.Tensor:
     """nnU-Net's per-class post-processing / the reference's `large_connected_domain` per organ, for a whole label map: every voxel
     whose component is not the largest of its label becomes 0 (`keep` = a voxel count: not of at least that many voxels).  Equal
     sizes: the component that comes last in memory order.  `classes` = None selects on every non-zero label, otherwise on the listed
     ones only and the others pass through.  One labelled pass whatever the number of classes; nothing is read back.
     With `fill_holes` every selected class present, in ascending order, then has its holes filled (`binary_fill_holes` of its mask);
     only voxels that are 0 at that moment receive the label.  This reads the per-label summary back once when `classes` is None.
-    -> uint8 labels."""
+    `connectivity` (1, 2, 3) is that of the components; nnU-Net labels at 3, where a vessel that hangs on its organ by an edge or a
+    corner stays.  The hole filling is at background connectivity 1 whatever it is.  -> uint8 labels."""
+    connectivity = ops_raw._connectivity(connectivity, "keep_largest_per_class")
     t = _label_volume(labels, "keep_largest_per_class")
     lib = L.get_lib()
     apply = None
@@ -197,7 +227,7 @@ def keep_largest_per_class(labels, classes: Optional[Sequence[int]] = None, keep
         table = torch.zeros(256, dtype=torch.uint8)
         table[classes] = 1
         apply = table.to(t.device)
-    out, info = _label_select(lib, t, keep, apply)
+    out, info = _label_select(lib, t, keep, apply, connectivity)
     if fill_holes:
         present = classes
         if present is None:
@@ -209,9 +239,10 @@ def keep_largest_per_class(labels, classes: Optional[Sequence[int]] = None, keep
     return out
 
 
-def class_component_summary(labels) -> dict:
-    """{label: (number of components, voxels of the largest)} for every label present: one labelled pass, one readback of 256 x 3
-    integers"""
+def class_component_summary(labels, connectivity: int = 1) -> dict:
+    """{label: (number of components at `connectivity`, voxels of the largest)} for every label present: one labelled pass, one
+    readback of 256 x 3 integers"""
+    connectivity = ops_raw._connectivity(connectivity, "class_component_summary")
     t = _label_volume(labels, "class_component_summary")
-    info = _label_select(L.get_lib(), t, "largest")[1].tolist()
+    info = _label_select(L.get_lib(), t, "largest", connectivity=connectivity)[1].tolist()
     return {c: (int(info[c][0]), int(info[c][2])) for c in range(1, 256) if info[c][0]}

@@ -312,18 +312,21 @@ class Predictor:
         from . import postprocess
         return postprocess.labels_from_logits(model_output, properties)
 
-    def save_to_nii(self, return_output, raw_spacing, save_dir, case_name, postprocess: bool = False) -> str:
+    def save_to_nii(self, return_output, raw_spacing, save_dir, case_name, postprocess: bool = False, connectivity: int = 1) -> str:
         """Write `<save_dir>/<case_name>.nii.gz` (reference :208-227).  `return_output`: a (D, H, W) label volume or mask, device tensor,
         host tensor or numpy array; it is cast to uint8 as the reference does.  `postprocess` runs `largest_connected_domain` on the
-        device (an empty mask stays empty where the reference raises).  `raw_spacing` goes to the header unpermuted, as the
-        reference passes it to `SetSpacing`.
+        device (an empty mask stays empty where the reference raises) with components at `connectivity` (1, 2, 3; the reference's 1 by
+        default; the holes are filled at background connectivity 1).  `raw_spacing` goes to the header unpermuted, as the reference
+        passes it to `SetSpacing`.
         A (C, D, H, W) input is refused unless C == 1: SimpleITK would turn a 4-D array into a 3-D VECTOR image, which nothing
         downstream of the reference reads as labels (4_predict.py passing its (3, ...) region stack is the reference's own loose end);
         write one file per channel instead.  -> the path written."""
         import os
 
         from . import nifti
+        from . import ops_raw
         from . import postprocess as post
+        connectivity = ops_raw._connectivity(connectivity, "save_to_nii")
         out = return_output
         shape = tuple(out.shape)
         if len(shape) == 4 and shape[0] == 1:
@@ -332,7 +335,7 @@ class Predictor:
             raise RuntimeError(f"save_to_nii: a (D, H, W) volume (or (1, D, H, W)) is required, got shape {shape}; a (C, D, H, W) stack "
                                "would become a vector image in the reference - write one file per channel")
         if postprocess:
-            out = post.largest_connected_domain(out)                       # uploads numpy / host tensors, stays on the device
+            out = post.largest_connected_domain(out, connectivity=connectivity)    # uploads numpy / host tensors, stays on the device
         if isinstance(out, torch.Tensor):
             out = out.to(torch.uint8).cpu().numpy()                        # the one copy to the host: one byte per voxel
         else:
@@ -344,17 +347,21 @@ class Predictor:
         print(f"{path} is saved successfully")
         return path
 
-    def save_organs_to_nii(self, labels, raw_spacing, save_dir, names: Sequence[str], postprocess: bool = False) -> List[str]:
+    def save_organs_to_nii(self, labels, raw_spacing, save_dir, names: Sequence[str], postprocess: bool = False,
+                           connectivity: int = 1) -> List[str]:
         """One file per organ of a multi-class label map: `<save_dir>/<names[i - 1]>.nii.gz` holds `labels == i` for i = 1 .. len(names)
         (the loop of the reference's light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:97-109).  `labels`: a (D, H, W)
         label volume, device tensor, host tensor or numpy array.  With `postprocess` each organ is `binary_fill_holes` of its largest
         component (`large_connected_domain` per organ); the largest components of all organs come from ONE labelled pass on the device
-        (segmamba_amd.postprocess.keep_largest_per_class).  One copy to the host: the uint8 label volume, or with `postprocess` the
+        (segmamba_amd.postprocess.keep_largest_per_class) with components at `connectivity` (1, 2, 3; holes at background connectivity
+        1).  One copy to the host: the uint8 label volume, or with `postprocess` the
         organs' filled masks packed eight to a byte (filled holes of different organs may overlap).  -> the paths written."""
         import os
 
         from . import nifti
+        from . import ops_raw
         from . import postprocess as post
+        connectivity = ops_raw._connectivity(connectivity, "save_organs_to_nii")
         names = [str(n) for n in names]
         if not 1 <= len(names) <= 255 or len(set(names)) != len(names):
             raise RuntimeError(f"save_organs_to_nii: between 1 and 255 distinct organ names are required, got {names}")
@@ -365,7 +372,7 @@ class Predictor:
             raise RuntimeError(f"save_organs_to_nii: a (D, H, W) label volume (or (1, D, H, W)) is required, got shape {shape}")
         n = len(names)
         if postprocess:
-            kept = post.keep_largest_per_class(labels, classes=range(1, n + 1))
+            kept = post.keep_largest_per_class(labels, classes=range(1, n + 1), connectivity=connectivity)
             packed = torch.zeros(((n + 7) // 8,) + tuple(kept.shape), dtype=torch.uint8, device=kept.device)
             for i in range(n):
                 packed[i // 8] |= post.binary_fill_holes(kept == i + 1) << (i % 8)
