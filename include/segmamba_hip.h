@@ -1048,7 +1048,7 @@ typedef struct segm_planes_bbox_args {
 int segm_planes_bbox(const segm_planes_bbox_args* args);
 
 /* ------------------------------------------------------------------------------------------------
- * Finishing a prediction on the device (additive to ABI 10; csrc/postprocess.hip).
+ * Finishing a prediction on the device (additive to ABI 10; csrc/postprocess.hip, csrc/ccl_roots.hip).
  * Replaces, of the reference's light_training/prediction.py: predict_raw_probability (:33-62) + the argmax of 4_predict.py:81 +
  * predict_noncrop_probability (:64-108) by ONE launch, and large_connected_domain (:17-27: skimage.measure.label at connectivity 1,
  * keep the largest, scipy.ndimage.binary_fill_holes) by connected components on the device.
@@ -1134,8 +1134,8 @@ typedef struct segm_ccl_select_args {
 size_t segm_ccl_select_workspace_bytes(int64_t voxels);
 int segm_ccl_select(const segm_ccl_select_args* args);
 
-/* Labelled connected components (additive to ABI 10; csrc/ccl_labels.hip): every class of a label map in ONE pass.  What the
- * reference's CT example needs per organ (4_predict_diffunet.py:97-109 writes `labels == i` per organ; prediction.py:17-27
+/* Labelled connected components (additive to ABI 10; csrc/ccl_roots.hip, csrc/ccl_labels.hip): every class of a label map in ONE pass.
+ * What the reference's CT example needs per organ (4_predict_diffunet.py:97-109 writes `labels == i` per organ; prediction.py:17-27
  * `large_connected_domain` keeps the largest component) and nnU-Net's "keep the largest component of every class".
  * Two voxels belong to one component when a path of face neighbours (connectivity 1) with the SAME NON-ZERO label joins them.
  *   roots[i] = -1 where the label is 0, otherwise the SMALLEST linear index of the voxel's component
@@ -1174,7 +1174,7 @@ typedef struct segm_ccl_label_select_args {
 size_t segm_ccl_label_select_workspace_bytes(int64_t voxels);
 int segm_ccl_label_select(const segm_ccl_label_select_args* args);
 
-/* Connected components at connectivity 1, 2 or 3 (additive to ABI 10; csrc/ccl_conn.hip).  `connectivity` c is that of
+/* Connected components at connectivity 1, 2 or 3 (additive to ABI 10; csrc/ccl_roots.hip).  `connectivity` c is that of
  * scipy.ndimage.generate_binary_structure(3, c) and skimage.measure.label(connectivity=c): two voxels are neighbours when their
  * offset has at most c non-zero coordinates, each of them +-1 - 6 (faces), 18 (faces and edges) or 26 (faces, edges and corners)
  * neighbours.  nnU-Net's post-processing, cc3d and the BraTS lesion-wise tooling label at full connectivity (3); the reference's

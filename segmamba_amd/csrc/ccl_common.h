@@ -1,5 +1,6 @@
-// What the binary (postprocess.hip) and the labelled (ccl_labels.hip) connected components share: the relaxed atomics on labels and
-// counts in both builds, the tile, the lock-free union-find on "labels only ever decrease", and the volume bound.
+// What the connected-component sources share (ccl_roots.hip: the roots; postprocess.hip, ccl_labels.hip: sizes and selection): the
+// relaxed atomics on labels and counts in both builds, the tile, the lock-free union-find on "labels only ever decrease", and the
+// volume bound.
 #pragma once
 #include "segm_device.h"
 
@@ -45,18 +46,6 @@ template <int S> __device__ __forceinline__ void lab_union(int32_t* L, int32_t a
         a = old;
     }
 }
-
-// the binary entry's kernel argument (postprocess.hip) and its last launch, which ccl_conn.hip makes as well: roots[i] = the end of
-// i's chain, -1 outside the mask.  It reads `lab`, `roots` and `N` only.
-struct CclDev {
-    const uint8_t* vol;
-    int32_t* lab;
-    int32_t* roots;
-    int32_t D, H, W, N;
-    int32_t bit, invert;
-    int32_t tx, ty;                     // tiles along x and y
-};
-__global__ void ccl_flatten_kernel(CclDev P);       // defined in postprocess.hip
 
 static inline bool ccl_volume_ok(int64_t d, int64_t h, int64_t w) {
     if (d <= 0 || h <= 0 || w <= 0) return false;

@@ -1,17 +1,8 @@
-// Connected components of a LABEL volume, every class in one pass, and the per-class selection
-// (C ABI: segm_ccl_label_roots, segm_ccl_label_select).
+// The selection per class of a label volume, from the roots of its components (C ABI: segm_ccl_label_select).
 //
-// The reference's CT example (light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:87-109) takes the argmax over 10
-// classes and writes `labels == i` per organ; `large_connected_domain` (light_training/prediction.py:17-27) keeps the largest
-// component of one binary mask.  Per organ through the binary entries of postprocess.hip that is nine passes over the volume; a
-// labelled volume holds every organ's components at once: two voxels are joined iff they are face neighbours with the SAME NON-ZERO
-// label.  The structure is that of the binary entry (64 x 4 x 4 tiles in LDS, face joins on agent-scope relaxed atomics, a flatten
-// pass; the root of a component is its smallest linear index).  What does not carry over from a binary mask:
-//   * a run along x ends where the label changes (`1 1 2 2` is two runs): the run starts are a ballot of "labelled and (lane 0 or the
-//     label differs from the left lane's)", not the zeros of the mask;
-//   * of adjacent voxels that both continue upwards only the first starts a union - but only when the two are one run: the second
-//     still starts its own when it is a run start (stripes one voxel wide along x);
-//   * the merge launch's `left` and `run` tests compare labels across the tile faces.
+// The reference's CT example (light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:87-109) writes `labels == i` per
+// organ and `large_connected_domain` (light_training/prediction.py:17-27) keeps the largest component of one binary mask.  The roots
+// of every class's components come from one labelled pass (ccl_roots.hip), their sizes from segm_ccl_sizes (postprocess.hip); here:
 //   * label_best_kernel    per label the maximum of (size << 32) | root and the number of roots: LDS atomics per workgroup, then one
 //                          64-bit atomic max and one add per label present in the workgroup (integers: any order, same bits).
 //   * label_select_kernel  a voxel keeps its label iff its root is its label's winner / its component is large enough; labels with
@@ -33,99 +24,8 @@ template <int S> __device__ __forceinline__ void key_max(u64_t* p, u64_t v) { __
 template <int S> __device__ __forceinline__ void key_add(u64_t* p, u64_t v) { __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, S); }
 #endif
 
-static_assert(kBlock == 256, "a thread per label value in the selection kernels, a wave per z of the tile");
+static_assert(kBlock == 256, "a thread per label value in the selection kernels");
 
-struct LabDev {
-    const uint8_t* vol;
-    int32_t* lab;
-    int32_t* roots;
-    int32_t D, H, W, N;
-    int32_t tx, ty;                     // tiles along x and y
-};
-
-__global__ void __launch_bounds__(kBlock) lccl_tile_kernel(LabDev P) {
-    __shared__ int32_t s_lab[kTileVox];
-    __shared__ uint8_t s_val[kTileVox];
-    __shared__ unsigned long long s_start[kTileRows];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t t = blockIdx.x;
-    const uint32_t bx = t % (uint32_t)P.tx;
-    t /= (uint32_t)P.tx;
-    const uint32_t by = t % (uint32_t)P.ty, bz = t / (uint32_t)P.ty;
-    const int x = (int)bx * kTX + lane, z = (int)bz * kTZ + wave;
-    int v[kTY];
-    // a run ends where the label changes: a voxel starts with the first voxel of its run along x
-#pragma unroll
-    for (int ly = 0; ly < kTY; ++ly) {
-        const int row = wave * kTY + ly, y = (int)by * kTY + ly;
-        v[ly] = 0;
-        if (x < P.W && y < P.H && z < P.D) v[ly] = (int)P.vol[((int64_t)z * P.H + y) * P.W + x];
-        const int left = __shfl(v[ly], (lane + 63) & 63);
-        const unsigned long long s = __ballot(v[ly] != 0 && (lane == 0 || left != v[ly]) ? 1 : 0);
-        if (lane == 0) s_start[row] = s;
-        const unsigned long long before = s & ((2ull << lane) - 1ull);       // the run starts at or left of this lane
-        s_val[row * kTX + lane] = (uint8_t)v[ly];
-        s_lab[row * kTX + lane] = v[ly] != 0 ? row * kTX + 63 - __builtin_clzll(before | 1ull) : -1;
-    }
-    __syncthreads();
-    // join with the row above in y and in z.  c: the voxel has the label of the one above.  Of two adjacent voxels of c the second
-    // needs no union when it continues the first one's run (then the two above are one run as well), and only then.
-#pragma unroll
-    for (int ly = 0; ly < kTY; ++ly) {
-        const int row = wave * kTY + ly;
-        const unsigned long long inner = ~s_start[row];                      // not the first voxel of a run
-        if (ly > 0) {
-            const unsigned long long c = __ballot(v[ly] != 0 && (int)s_val[(row - 1) * kTX + lane] == v[ly] ? 1 : 0);
-            if (((c & ~((c << 1) & inner)) >> lane) & 1ull) lab_union<kScopeWorkgroup>(s_lab, row * kTX + lane, (row - 1) * kTX + lane);
-        }
-        if (wave > 0) {
-            const unsigned long long c = __ballot(v[ly] != 0 && (int)s_val[(row - kTY) * kTX + lane] == v[ly] ? 1 : 0);
-            if (((c & ~((c << 1) & inner)) >> lane) & 1ull) lab_union<kScopeWorkgroup>(s_lab, row * kTX + lane, (row - kTY) * kTX + lane);
-        }
-    }
-    __syncthreads();
-    // local index order = global index order inside a tile, so the local root is the tile's smallest global index of the component
-    for (int ly = 0; ly < kTY; ++ly) {
-        const int row = wave * kTY + ly, y = (int)by * kTY + ly;
-        if (!(x < P.W && y < P.H && z < P.D)) continue;
-        int32_t l = s_lab[row * kTX + lane];
-        if (l >= 0) {
-            while (s_lab[l] != l) l = s_lab[l];
-            const int rz = l / (kTX * kTY), ry = (l / kTX) % kTY, rx = l % kTX;
-            l = (int32_t)((((int64_t)bz * kTZ + rz) * P.H + ((int64_t)by * kTY + ry)) * P.W + (int64_t)bx * kTX + rx);
-        }
-        P.lab[((int64_t)z * P.H + y) * P.W + x] = l;
-    }
-}
-
-// voxels on the low faces of their tile are joined with the equally labelled neighbour across the face; every access to a label in
-// this launch is an agent-scope relaxed atomic (lab_union)
-__global__ void __launch_bounds__(kBlock) lccl_merge_kernel(LabDev P) {
-    const uint32_t i = (uint32_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (uint32_t)P.N) return;
-    const uint8_t v = P.vol[i];
-    if (v == 0) return;
-    const uint32_t W = (uint32_t)P.W, HW = (uint32_t)P.H * W;
-    const uint32_t z = i / HW, rem = i - z * HW, y = rem / W, x = rem - y * W;
-    const bool onx = (x % kTX) == 0, ony = (y % kTY) == 0 && y > 0, onz = (z % kTZ) == 0 && z > 0;
-    if (!(onx || ony || onz)) return;
-    const bool left = x > 0 && P.vol[i - 1] == v;
-    if (onx && left) lab_union<kScopeAgent>(P.lab, (int32_t)i, (int32_t)(i - 1));
-    const bool run = left && !onx;                    // the left neighbour is in this tile, has this label: one component already
-    if (ony && P.vol[i - W] == v && !(run && P.vol[i - W - 1] == v)) lab_union<kScopeAgent>(P.lab, (int32_t)i, (int32_t)(i - W));
-    if (onz && P.vol[i - HW] == v && !(run && P.vol[i - HW - 1] == v)) lab_union<kScopeAgent>(P.lab, (int32_t)i, (int32_t)(i - HW));
-}
-
-__global__ void __launch_bounds__(kBlock) lccl_flatten_kernel(LabDev P) {
-    const uint32_t i = (uint32_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (uint32_t)P.N) return;
-    int32_t l = P.lab[i];
-    if (l >= 0)
-        while (P.lab[l] != l) l = P.lab[l];
-    P.roots[i] = l;
-}
-
-// ---- selection per label --------------------------------------------------------------------------------------------------------------
 struct LabSelDev {
     const uint8_t* vol;
     const int32_t* roots;
@@ -189,33 +89,6 @@ __global__ void __launch_bounds__(kBlock) label_select_kernel(LabSelDev P) {
 }  // namespace segm
 
 using namespace segm;
-
-extern "C" size_t segm_ccl_label_roots_workspace_bytes(int64_t voxels) {
-    if (voxels <= 0 || voxels > SEGM_CCL_MAX_VOXELS) return 0;
-    return (size_t)voxels * sizeof(int32_t);
-}
-
-extern "C" int segm_ccl_label_roots(const segm_ccl_label_roots_args* a) {
-    if (!a) return SEGM_E_NULL;
-    if (!a->labels || !a->roots) return SEGM_E_NULL;
-    if (!ccl_volume_ok(a->depth, a->height, a->width)) return SEGM_E_SHAPE;
-    if ((uintptr_t)a->roots % sizeof(int32_t)) return SEGM_E_SHAPE;
-    const int64_t N = (int64_t)a->depth * a->height * a->width;
-    if (!a->workspace || a->workspace_bytes < segm_ccl_label_roots_workspace_bytes(N) || (uintptr_t)a->workspace % sizeof(int32_t)) return SEGM_E_WORKSPACE;
-    LabDev P;
-    memset(&P, 0, sizeof(P));
-    P.vol = a->labels; P.lab = (int32_t*)a->workspace; P.roots = a->roots;
-    P.D = a->depth; P.H = a->height; P.W = a->width; P.N = (int32_t)N;
-    P.tx = (a->width + kTX - 1) / kTX;
-    P.ty = (a->height + kTY - 1) / kTY;
-    const int64_t tiles = (int64_t)P.tx * P.ty * ((a->depth + kTZ - 1) / kTZ);      // <= N: every tile holds a voxel
-    hipStream_t st = (hipStream_t)a->stream;
-    const dim3 flat((unsigned)((N + kBlock - 1) / kBlock)), block(kBlock);
-    hipLaunchKernelGGL(lccl_tile_kernel, dim3((unsigned)tiles), block, 0, st, P);
-    hipLaunchKernelGGL(lccl_merge_kernel, flat, block, 0, st, P);
-    hipLaunchKernelGGL(lccl_flatten_kernel, flat, block, 0, st, P);
-    return (int)hipGetLastError();
-}
 
 extern "C" size_t segm_ccl_label_select_workspace_bytes(int64_t voxels) {
     if (voxels <= 0 || voxels > SEGM_CCL_MAX_VOXELS) return 0;

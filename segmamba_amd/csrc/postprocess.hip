@@ -1,5 +1,5 @@
-// Finishing a prediction on the device: logits -> label volume in one pass, connected components, component sizes and selection
-// (C ABI: segm_resample_argmax, segm_ccl_roots, segm_ccl_sizes, segm_ccl_select).
+// Finishing a prediction on the device: logits -> label volume in one pass, component sizes and selection
+// (C ABI: segm_resample_argmax, segm_ccl_sizes, segm_ccl_select; the roots of the components: ccl_roots.hip).
 //
 // Replaces what the reference does between `maybe_mirror_and_predict` and the file on disk (light_training/prediction.py):
 // `predict_raw_probability` (:33-62, one trilinear interpolation per class into a second full fp32 volume), the `argmax` of
@@ -10,19 +10,6 @@
 //                              False, fp32), keeps the first largest and stores the four labels as one dword.  The logits are read once
 //                              (the eight corners of neighbouring outputs meet in the cache; at identity size one 16-byte packet per
 //                              class and thread); optionally the region bit planes of the label go out with it.
-//   * connected components     block-based union-find.  The root of a component is DEFINED as its smallest linear voxel index, so the
-//                              result does not depend on the order of anything.
-//       ccl_tile_kernel        a workgroup owns a 64 x 4 x 4 tile, a wave a row along x: the row's mask is one ballot, a voxel starts at
-//                              the first voxel of its run (clz), runs are joined with the rows above (y, z) by union-find on LDS atomic
-//                              min, and every voxel leaves with the global index of its tile-local root.
-//       ccl_merge_kernel       voxels on the low faces of their tile are joined with the neighbour across the face: the same union-find
-//                              on the global labels.  EVERY access to a label in this launch is an agent-scope relaxed atomic
-//                              (__hip_atomic_load / __hip_atomic_fetch_min: they bypass the per-CU L1 and are served where all XCDs
-//                              agree); labels only ever decrease and always name a voxel of the same component, no workgroup waits for
-//                              another, so the loops end whatever the order.  Of a run of face voxels only the first starts a union.
-//       ccl_flatten_kernel     roots[i] = the end of i's chain (the labels are read-only in this launch: plain loads).
-//     Cost of a call: 3 launches and no readback, whatever the volume and the shape of the mask.  A chain is as long as the number
-//     of tiles a path crosses at worst (the serpentine), and is walked by the one thread that owns the voxel.
 //   * ccl_sizes_kernel         counts per root by integer atomic add (exact), aggregated per thread over runs of equal roots and per
 //                              workgroup for the workgroup's commonest root; flags the roots whose component touches a face.
 //   * ccl_select               arg-max over (count, root index) as one 64-bit key - equal counts: the LAST root wins - by per-workgroup
@@ -150,88 +137,6 @@ static void launch_resample(const ResDev& P, bool ident, hipStream_t st) {
     const dim3 grid((P.nthreads + kBlock - 1) / kBlock), block(kBlock);
     if (ident) hipLaunchKernelGGL((resample_argmax_kernel<T, true>), grid, block, 0, st, P);
     else hipLaunchKernelGGL((resample_argmax_kernel<T, false>), grid, block, 0, st, P);
-}
-
-// ---- connected components -----------------------------------------------------------------------------------------------------------
-// struct CclDev: ccl_common.h (ccl_conn.hip launches ccl_flatten_kernel with it)
-__device__ __forceinline__ bool ccl_inside(uint32_t v, int bit, int invert) {
-    const int in = bit >= 0 ? (int)((v >> bit) & 1u) : (int)(v != 0u);
-    return in != invert;
-}
-
-__global__ void __launch_bounds__(kBlock) ccl_tile_kernel(CclDev P) {
-    __shared__ int32_t s_lab[kTileVox];
-    __shared__ unsigned long long s_mask[kTileRows];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t t = blockIdx.x;
-    const uint32_t bx = t % (uint32_t)P.tx;
-    t /= (uint32_t)P.tx;
-    const uint32_t by = t % (uint32_t)P.ty, bz = t / (uint32_t)P.ty;
-    const int x = (int)bx * kTX + lane, z = (int)bz * kTZ + wave;
-    // a row's mask is one ballot; a voxel starts with the first voxel of its run along x
-    for (int ly = 0; ly < kTY; ++ly) {
-        const int row = wave * kTY + ly, y = (int)by * kTY + ly;
-        bool in = false;
-        if (x < P.W && y < P.H && z < P.D) in = ccl_inside(P.vol[((int64_t)z * P.H + y) * P.W + x], P.bit, P.invert);
-        const unsigned long long m = __ballot(in ? 1 : 0);
-        if (lane == 0) s_mask[row] = m;
-        const unsigned long long zl = ~m & ((1ull << lane) - 1ull);
-        const int start = zl ? 64 - __builtin_clzll(zl) : 0;
-        s_lab[row * kTX + lane] = in ? row * kTX + start : -1;
-    }
-    __syncthreads();
-    // join with the row above in y and in z; of adjacent voxels that both have an upper neighbour only the first needs to
-    for (int ly = 0; ly < kTY; ++ly) {
-        const int row = wave * kTY + ly;
-        const unsigned long long m = s_mask[row];
-        if (ly > 0) {
-            const unsigned long long c = m & s_mask[row - 1];
-            if (((c & ~(c << 1)) >> lane) & 1ull) lab_union<kScopeWorkgroup>(s_lab, row * kTX + lane, (row - 1) * kTX + lane);
-        }
-        if (wave > 0) {
-            const unsigned long long c = m & s_mask[row - kTY];
-            if (((c & ~(c << 1)) >> lane) & 1ull) lab_union<kScopeWorkgroup>(s_lab, row * kTX + lane, (row - kTY) * kTX + lane);
-        }
-    }
-    __syncthreads();
-    // local index order = global index order inside a tile, so the local root is the tile's smallest global index of the component
-    for (int ly = 0; ly < kTY; ++ly) {
-        const int row = wave * kTY + ly, y = (int)by * kTY + ly;
-        if (!(x < P.W && y < P.H && z < P.D)) continue;
-        int32_t l = s_lab[row * kTX + lane];
-        if (l >= 0) {
-            while (s_lab[l] != l) l = s_lab[l];
-            const int rz = l / (kTX * kTY), ry = (l / kTX) % kTY, rx = l % kTX;
-            l = (int32_t)((((int64_t)bz * kTZ + rz) * P.H + ((int64_t)by * kTY + ry)) * P.W + (int64_t)bx * kTX + rx);
-        }
-        P.lab[((int64_t)z * P.H + y) * P.W + x] = l;
-    }
-}
-
-__global__ void __launch_bounds__(kBlock) ccl_merge_kernel(CclDev P) {
-    const uint32_t i = (uint32_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (uint32_t)P.N) return;
-    if (!ccl_inside(P.vol[i], P.bit, P.invert)) return;
-    const uint32_t W = (uint32_t)P.W, HW = (uint32_t)P.H * W;
-    const uint32_t z = i / HW, rem = i - z * HW, y = rem / W, x = rem - y * W;
-    const bool onx = (x % kTX) == 0, ony = (y % kTY) == 0 && y > 0, onz = (z % kTZ) == 0 && z > 0;
-    if (!(onx || ony || onz)) return;
-    const bool left = x > 0 && ccl_inside(P.vol[i - 1], P.bit, P.invert);
-    if (onx && left) lab_union<kScopeAgent>(P.lab, (int32_t)i, (int32_t)(i - 1));
-    const bool run = left && !onx;                    // the left neighbour is in this tile and already one component with this voxel
-    if (ony && ccl_inside(P.vol[i - W], P.bit, P.invert) && !(run && ccl_inside(P.vol[i - W - 1], P.bit, P.invert)))
-        lab_union<kScopeAgent>(P.lab, (int32_t)i, (int32_t)(i - W));
-    if (onz && ccl_inside(P.vol[i - HW], P.bit, P.invert) && !(run && ccl_inside(P.vol[i - HW - 1], P.bit, P.invert)))
-        lab_union<kScopeAgent>(P.lab, (int32_t)i, (int32_t)(i - HW));
-}
-
-__global__ void __launch_bounds__(kBlock) ccl_flatten_kernel(CclDev P) {
-    const uint32_t i = (uint32_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= (uint32_t)P.N) return;
-    int32_t l = P.lab[i];
-    if (l >= 0)
-        while (P.lab[l] != l) l = P.lab[l];
-    P.roots[i] = l;
 }
 
 // ---- sizes ----------------------------------------------------------------------------------------------------------------------------
@@ -389,35 +294,6 @@ extern "C" int segm_resample_argmax(const segm_resample_argmax_args* a) {
     if (a->dtype == SEGM_F32) launch_resample<float>(P, ident, st);
     else if (a->dtype == SEGM_F16) launch_resample<f16_t>(P, ident, st);
     else launch_resample<bf16_t>(P, ident, st);
-    return (int)hipGetLastError();
-}
-
-extern "C" size_t segm_ccl_roots_workspace_bytes(int64_t voxels) {
-    if (voxels <= 0 || voxels > SEGM_CCL_MAX_VOXELS) return 0;
-    return (size_t)voxels * sizeof(int32_t);
-}
-
-extern "C" int segm_ccl_roots(const segm_ccl_roots_args* a) {
-    if (!a) return SEGM_E_NULL;
-    if (!a->volume || !a->roots) return SEGM_E_NULL;
-    if (!ccl_volume_ok(a->depth, a->height, a->width)) return SEGM_E_SHAPE;
-    if (a->bit < -1 || a->bit > 7 || (a->invert != 0 && a->invert != 1)) return SEGM_E_SHAPE;
-    if ((uintptr_t)a->roots % sizeof(int32_t)) return SEGM_E_SHAPE;
-    const int64_t N = (int64_t)a->depth * a->height * a->width;
-    if (!a->workspace || a->workspace_bytes < segm_ccl_roots_workspace_bytes(N) || (uintptr_t)a->workspace % sizeof(int32_t)) return SEGM_E_WORKSPACE;
-    CclDev P;
-    memset(&P, 0, sizeof(P));
-    P.vol = a->volume; P.lab = (int32_t*)a->workspace; P.roots = a->roots;
-    P.D = a->depth; P.H = a->height; P.W = a->width; P.N = (int32_t)N;
-    P.bit = a->bit; P.invert = a->invert;
-    P.tx = (a->width + kTX - 1) / kTX;
-    P.ty = (a->height + kTY - 1) / kTY;
-    const int64_t tiles = (int64_t)P.tx * P.ty * ((a->depth + kTZ - 1) / kTZ);      // <= N: every tile holds a voxel
-    hipStream_t st = (hipStream_t)a->stream;
-    const dim3 flat((unsigned)((N + kBlock - 1) / kBlock)), block(kBlock);
-    hipLaunchKernelGGL(ccl_tile_kernel, dim3((unsigned)tiles), block, 0, st, P);
-    hipLaunchKernelGGL(ccl_merge_kernel, flat, block, 0, st, P);
-    hipLaunchKernelGGL(ccl_flatten_kernel, flat, block, 0, st, P);
     return (int)hipGetLastError();
 }
 

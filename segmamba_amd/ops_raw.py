@@ -1973,7 +1973,7 @@ def border_stats(lib: L.SegmLib, borders: torch.Tensor, edt: torch.Tensor, items
 
 
 # ---------------------------------------------------------------------------------------------------------
-# finishing a prediction (csrc/postprocess.hip): logits -> labels, connected components, sizes, selection
+# finishing a prediction (csrc/postprocess.hip, csrc/ccl_roots.hip): logits -> labels, connected components, sizes, selection
 # ---------------------------------------------------------------------------------------------------------
 def _same_volume(t, what: str, dtype, shape, device) -> None:
     """a caller's buffer: dtype, shape, device and contiguity before its pointer leaves Python"""
@@ -2059,7 +2059,7 @@ def _connectivity(connectivity, what: str) -> int:
 def ccl_roots(lib: L.SegmLib, volume: torch.Tensor, bit: int = -1, invert: bool = False, out: torch.Tensor = None,
               connectivity: int = 1) -> torch.Tensor:
     """Connected components of the mask `(volume >> bit) & 1` (bit = -1: `volume != 0`), or of its complement with `invert`, at
-    `connectivity` 1, 2 or 3 (6, 18 or 26 neighbours; 1 calls segm_ccl_roots, 2 and 3 segm_ccl_roots_conn).  volume (D, H, W) uint8.
+    `connectivity` 1, 2 or 3 (6, 18 or 26 neighbours).  volume (D, H, W) uint8.
     -> int32 (D, H, W): -1 outside the mask, else the smallest linear index of the voxel's component."""
     connectivity = _connectivity(connectivity, "ccl_roots")
     _ccl_volume(volume, "ccl_roots: volume")
@@ -2072,15 +2072,11 @@ def ccl_roots(lib: L.SegmLib, volume: torch.Tensor, bit: int = -1, invert: bool 
         _same_volume(out, "ccl_roots: out", torch.int32, volume.shape, volume.device)
     nbytes = lib.dll.segm_ccl_roots_workspace_bytes(volume.numel())
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=volume.device)
-    a = L.CclRootsArgs() if connectivity == 1 else L.CclRootsConnArgs()
+    a = L.CclRootsConnArgs()
     a.depth, a.height, a.width = volume.shape
-    a.bit, a.invert = bit, 1 if invert else 0
+    a.bit, a.invert, a.connectivity = bit, 1 if invert else 0, connectivity
     a.volume, a.roots, a.workspace, a.workspace_bytes, a.stream = volume.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(volume)
-    if connectivity == 1:
-        lib.check(lib.dll.segm_ccl_roots(a), "ccl_roots")
-    else:
-        a.connectivity = connectivity
-        lib.check(lib.dll.segm_ccl_roots_conn(a), "ccl_roots")
+    lib.check(lib.dll.segm_ccl_roots_conn(a), "ccl_roots")
     return out
 
 
@@ -2130,9 +2126,9 @@ def ccl_select(lib: L.SegmLib, roots: torch.Tensor, sizes: torch.Tensor, mode: i
 
 def ccl_label_roots(lib: L.SegmLib, labels: torch.Tensor, out: torch.Tensor = None, connectivity: int = 1) -> torch.Tensor:
     """Connected components of every class of a label volume in one pass: two voxels are joined by a path of neighbours of the same
-    non-zero label, at `connectivity` 1, 2 or 3 (6, 18 or 26 neighbours; 1 calls segm_ccl_label_roots, 2 and 3
-    segm_ccl_label_roots_conn).  labels (D, H, W) uint8.  -> int32 (D, H, W): -1 where the label is 0, else the smallest linear index
-    of the voxel's component (on `labels == k` what `ccl_roots(labels == k)` gives at the same connectivity)."""
+    non-zero label, at `connectivity` 1, 2 or 3 (6, 18 or 26 neighbours).  labels (D, H, W) uint8.  -> int32 (D, H, W): -1 where the
+    label is 0, else the smallest linear index of the voxel's component (on `labels == k` what `ccl_roots(labels == k)` gives at the
+    same connectivity)."""
     connectivity = _connectivity(connectivity, "ccl_label_roots")
     _ccl_volume(labels, "ccl_label_roots: labels")
     if out is None:
@@ -2141,14 +2137,10 @@ def ccl_label_roots(lib: L.SegmLib, labels: torch.Tensor, out: torch.Tensor = No
         _same_volume(out, "ccl_label_roots: out", torch.int32, labels.shape, labels.device)
     nbytes = lib.dll.segm_ccl_label_roots_workspace_bytes(labels.numel())
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
-    a = L.CclLabelRootsArgs() if connectivity == 1 else L.CclLabelRootsConnArgs()
-    a.depth, a.height, a.width = labels.shape
+    a = L.CclLabelRootsConnArgs()
+    a.depth, a.height, a.width, a.connectivity = *labels.shape, connectivity
     a.labels, a.roots, a.workspace, a.workspace_bytes, a.stream = labels.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(labels)
-    if connectivity == 1:
-        lib.check(lib.dll.segm_ccl_label_roots(a), "ccl_label_roots")
-    else:
-        a.connectivity = connectivity
-        lib.check(lib.dll.segm_ccl_label_roots_conn(a), "ccl_label_roots")
+    lib.check(lib.dll.segm_ccl_label_roots_conn(a), "ccl_label_roots")
     return out
 
 

@@ -1,4 +1,5 @@
-"""Finishing a prediction on the device: logits -> label volume, connected components, hole filling (csrc/postprocess.hip).
+"""Finishing a prediction on the device: logits -> label volume, connected components, hole filling (csrc/postprocess.hip,
+csrc/ccl_roots.hip).
 
 The stage of the reference's pipeline between `maybe_mirror_and_predict` and the file on disk (4_predict.py:75-99 on
 light_training/prediction.py): resample the logits to the pre-resample crop shape, arg-max, paste into the un-cropped volume
@@ -9,7 +10,7 @@ call reads a volume back.
 
 `connectivity` is 1, 2 or 3 as in `scipy.ndimage.generate_binary_structure(3, c)` and `skimage.measure.label(connectivity=c)`: 6
 (faces), 18 (faces and edges) or 26 (faces, edges and corners) neighbours.  The default everywhere is 1, which is what the reference's
-`large_connected_domain` passes; nnU-Net's post-processing, cc3d and the BraTS lesion-wise tooling label at 3 (csrc/ccl_conn.hip).
+`large_connected_domain` passes; nnU-Net's post-processing, cc3d and the BraTS lesion-wise tooling label at 3.
 It is the connectivity of the FOREGROUND components.  Where a function also fills holes (`largest_connected_domain`,
 `postprocess_labels`, `keep_largest_per_class(fill_holes=True)`) the background flood stays at connectivity 1 whatever the foreground's:
 that is `measure.label(connectivity=c)` followed by `ndimage.binary_fill_holes(...)` with its default structure, and the topologically
@@ -25,7 +26,8 @@ Where this deliberately differs from the reference:
 
 Multi-organ label maps (the reference's CT example, light_training/examples/AbdomenAtlas1.0Mini/4_predict_diffunet.py:87-109: the
 argmax over 10 classes, one file per organ): `labels_from_logits` takes up to 32 classes, and `keep_largest_per_class` keeps the
-largest component of every class from ONE labelled connected-components pass (csrc/ccl_labels.hip) instead of one pass per class.
+largest component of every class from ONE labelled connected-components pass (csrc/ccl_roots.hip, csrc/ccl_labels.hip)
+instead of one pass per class.
 """
 from __future__ import annotations
 
@@ -175,7 +177,7 @@ def postprocess_labels(labels, regions: Sequence[Sequence[int]] = BRATS_REGIONS,
     return out
 
 
-# ---- every class of a label map in one pass (csrc/ccl_labels.hip) ----------------------------------------------------------------------
+# ---- every class of a label map in one pass (csrc/ccl_roots.hip, csrc/ccl_labels.hip) ---------------------------------------------------
 def _label_volume(x, what: str) -> torch.Tensor:
     """uint8, contiguous, (D, H, W), on the device; integer label maps of other types are converted"""
     t = _to_device(x)

@@ -1,5 +1,5 @@
 """Checks shared by tests/test_emu_ccl_conn.py (kernel sources on the CPU emulator) and tests/test_gpu_ccl_conn.py (the HIP library):
-connected components at connectivity 1, 2 and 3 (csrc/ccl_conn.hip), of a mask and per class of a label volume, and the `connectivity`
+connected components at connectivity 1, 2 and 3 (csrc/ccl_roots.hip), of a mask and per class of a label volume, and the `connectivity`
 keyword of the host functions above them.  Every function takes the loaded library and the device its tensors live on.  References:
 tests/ccl_conn_ref.py (numpy, no scipy).  Every comparison is exact; nothing here has a tolerance."""
 import importlib.util
@@ -29,7 +29,7 @@ def dev_t(a, dev):
 
 
 def conn_roots(lib, volume, bit, invert, c):
-    """segm_ccl_roots_conn itself, at every c (ops_raw.ccl_roots sends c = 1 to segm_ccl_roots)"""
+    """segm_ccl_roots_conn itself, at every c"""
     out = torch.full(volume.shape, -7, dtype=torch.int32, device=volume.device)
     nbytes = lib.dll.segm_ccl_roots_workspace_bytes(volume.numel())
     ws = torch.empty(nbytes // 4, dtype=torch.int32, device=volume.device)
@@ -50,6 +50,30 @@ def conn_label_roots(lib, labels, c):
     a.connectivity = c
     a.labels, a.roots, a.workspace, a.workspace_bytes, a.stream = labels.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(labels)
     lib.check(lib.dll.segm_ccl_label_roots_conn(a), "segm_ccl_label_roots_conn")
+    return out
+
+
+def legacy_roots(lib, volume, bit=-1, invert=0, reserved=0):
+    """segm_ccl_roots itself, with its own struct (ops_raw.ccl_roots calls segm_ccl_roots_conn at every c)"""
+    out = torch.full(volume.shape, -7, dtype=torch.int32, device=volume.device)
+    nbytes = lib.dll.segm_ccl_roots_workspace_bytes(volume.numel())
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=volume.device)
+    a = L.CclRootsArgs()
+    a.depth, a.height, a.width = volume.shape
+    a.bit, a.invert, a.reserved = bit, invert, reserved
+    a.volume, a.roots, a.workspace, a.workspace_bytes, a.stream = volume.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(volume)
+    lib.check(lib.dll.segm_ccl_roots(a), "segm_ccl_roots")
+    return out
+
+
+def legacy_label_roots(lib, labels, reserved=0):
+    out = torch.full(labels.shape, -7, dtype=torch.int32, device=labels.device)
+    nbytes = lib.dll.segm_ccl_label_roots_workspace_bytes(labels.numel())
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=labels.device)
+    a = L.CclLabelRootsArgs()
+    a.depth, a.height, a.width, a.reserved = *labels.shape, reserved
+    a.labels, a.roots, a.workspace, a.workspace_bytes, a.stream = labels.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes, L.stream_handle(labels)
+    lib.check(lib.dll.segm_ccl_label_roots(a), "segm_ccl_label_roots")
     return out
 
 
@@ -82,9 +106,9 @@ def check_mask(lib, dev, name):
             assert torch.equal(got, ops_raw.ccl_roots(lib, dev_t(1 - m, dev), invert=True, connectivity=c)), (name, c)
             assert torch.equal(inv, ops_raw.ccl_roots(lib, t, invert=True, connectivity=c)), (name, c, "inverted")
             assert torch.equal(PP.component_roots(t, connectivity=c), got)
-    assert torch.equal(conn_roots(lib, t, -1, 0, 1), ops_raw.ccl_roots(lib, t))               # c = 1: the existing entry's result
+    assert torch.equal(conn_roots(lib, t, -1, 0, 1), legacy_roots(lib, t))                    # c = 1: the existing entry's result
     if small:
-        assert torch.equal(conn_roots(lib, packed, bit, 1, 1), ops_raw.ccl_roots(lib, packed, bit=bit, invert=True))
+        assert torch.equal(conn_roots(lib, packed, bit, 1, 1), legacy_roots(lib, packed, bit, 1))
         assert torch.equal(conn_roots(lib, t, -1, 0, 3), ops_raw.ccl_roots(lib, t, connectivity=3))
     assert np.array_equal(t.cpu().numpy(), m)                             # the input is not modified
 
@@ -136,10 +160,23 @@ def check_labels(lib, dev, name):
         assert ops_raw.ccl_label_roots(lib, t, out=buf, connectivity=c) is buf and torch.equal(buf, roots)      # the second call
         if lab.size <= SMALL:
             assert torch.equal(PP.label_component_roots(t, connectivity=c), roots)
-    assert torch.equal(conn_label_roots(lib, t, 1), ops_raw.ccl_label_roots(lib, t))          # c = 1: the existing entry's result
+    assert torch.equal(conn_label_roots(lib, t, 1), legacy_label_roots(lib, t))               # c = 1: the existing entry's result
     if lab.size <= SMALL:
         assert torch.equal(conn_label_roots(lib, t, 3), ops_raw.ccl_label_roots(lib, t, connectivity=3))
     assert np.array_equal(t.cpu().numpy(), lab)
+
+
+def check_legacy_entries_ignore_reserved(lib, dev):
+    """segm_ccl_roots and segm_ccl_label_roots are connectivity 1 whatever their `reserved` field holds: with reserved = 3, the value
+    that the layout-identical *_conn struct reads as its connectivity, the roots are the reference at 1, which differs from that at 3
+    (hand case: 5 against 3 components)"""
+    for got, want1, want3 in (
+            (legacy_roots(lib, dev_t(CR.mask("hand"), dev), reserved=3), CR.mask_roots("hand", 1), CR.mask_roots("hand", 3)),
+            (legacy_label_roots(lib, dev_t(CR.labels("diagonal_island"), dev), reserved=3), CR.labels_roots("diagonal_island", 1),
+             CR.labels_roots("diagonal_island", 3))):
+        assert not np.array_equal(want1, want3) and CR.components(want1) > CR.components(want3)
+        assert np.array_equal(got.cpu().numpy(), want1)
+    assert CR.components(CR.mask_roots("hand", 1)) == 5 and CR.components(CR.mask_roots("hand", 3)) == 3
 
 
 # ---- 3. the host functions ----------------------------------------------------------------------------------------------------------------

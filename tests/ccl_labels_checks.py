@@ -1,5 +1,5 @@
 """Checks shared by tests/test_emu_ccl_labels.py (kernel sources on the CPU emulator) and tests/test_gpu_ccl_labels.py (the HIP
-library): labelled connected components (csrc/ccl_labels.hip), the per-class selection, the arg-max beyond 8 classes and the host
+library): labelled connected components (csrc/ccl_roots.hip, csrc/ccl_labels.hip), the per-class selection, the arg-max beyond 8 classes and the host
 functions on top.  Every function takes the loaded library and the device its tensors live on.  References: tests/ccl_labels_ref.py.
 Every comparison is exact (array_equal); nothing here has a tolerance."""
 import importlib.util

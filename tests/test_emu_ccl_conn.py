@@ -1,4 +1,4 @@
-"""Connected components at connectivity 1, 2 and 3 (csrc/ccl_conn.hip) and the `connectivity` keyword of the host functions, with the
+"""Connected components at connectivity 1, 2 and 3 (csrc/ccl_roots.hip) and the `connectivity` keyword of the host functions, with the
 kernel sources compiled for the CPU emulator.  References: tests/ccl_conn_ref.py (numpy; pinned to scipy.ndimage.label here).  The same
 checks run on the HIP library in tests/test_gpu_ccl_conn.py."""
 import pytest
@@ -49,6 +49,10 @@ def test_mask_roots_emulated(product, case):
 def test_label_roots_emulated(product, case):
     """per class what the binary entry gives at the same c, -1 on the background, different labels never joined, two calls bit-equal"""
     K.check_labels(product, "cpu", case)
+
+
+def test_legacy_entries_ignore_reserved_emulated(emu):
+    K.check_legacy_entries_ignore_reserved(emu, "cpu")
 
 
 @pytest.mark.parametrize("case", HOST_CASES)

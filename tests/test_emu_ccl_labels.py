@@ -1,4 +1,4 @@
-"""Labelled connected components (csrc/ccl_labels.hip), the per-class selection, the arg-max beyond 8 classes and the host functions on
+"""Labelled connected components (csrc/ccl_roots.hip, csrc/ccl_labels.hip), the per-class selection, the arg-max beyond 8 classes and the host functions on
 top, with the kernel sources compiled for the CPU emulator.  References: tests/ccl_labels_ref.py (numpy; scipy.ndimage where it
 imports).  The same checks run on the HIP library in tests/test_gpu_ccl_labels.py."""
 import pytest

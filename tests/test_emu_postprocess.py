@@ -1,6 +1,6 @@
-"""Device-side prediction finishing (segmamba_amd/postprocess.py on csrc/postprocess.hip) with the kernel sources compiled for the CPU
-emulator: connected components, sizes, selection, hole filling, numbering, the logits -> label map kernel, wrapper refusals and the
-exports.  References: tests/postprocess_ref.py (numpy restatements; scipy.ndimage where it imports).  The same checks run on the HIP
+"""Device-side prediction finishing (segmamba_amd/postprocess.py on csrc/postprocess.hip and csrc/ccl_roots.hip) with the
+kernel sources compiled for the CPU emulator: connected components, sizes, selection, hole filling, numbering, the logits -> label
+map kernel, wrapper refusals and the exports.  References: tests/postprocess_ref.py (numpy restatements; scipy.ndimage where it imports).  The same checks run on the HIP
 library in tests/test_gpu_postprocess.py."""
 import numpy as np
 import pytest

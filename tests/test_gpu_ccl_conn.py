@@ -1,4 +1,4 @@
-"""Connected components at connectivity 1, 2 and 3 (csrc/ccl_conn.hip) and what is built on them, on the HIP library: the checks of
+"""Connected components at connectivity 1, 2 and 3 (csrc/ccl_roots.hip) and what is built on them, on the HIP library: the checks of
 tests/test_emu_ccl_conn.py on the GPU, plus one 96 x 160 x 160 ten-class volume at connectivity 3 against the per-class loop."""
 import pytest
 import torch
@@ -27,6 +27,10 @@ def test_mask_roots(hip, case):
 @pytest.mark.parametrize("case", sorted(CR.LABELS))
 def test_label_roots(hip, case):
     K.check_labels(hip, DEV, case)
+
+
+def test_legacy_entries_ignore_reserved(hip):
+    K.check_legacy_entries_ignore_reserved(hip, DEV)
 
 
 @pytest.mark.parametrize("case", HOST_CASES)

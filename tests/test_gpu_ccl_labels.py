@@ -1,4 +1,4 @@
-"""Labelled connected components (csrc/ccl_labels.hip) and what is built on them, on the HIP library: the checks of
+"""Labelled connected components (csrc/ccl_roots.hip, csrc/ccl_labels.hip) and what is built on them, on the HIP library: the checks of
 tests/test_emu_ccl_labels.py on the GPU, plus one 96 x 160 x 160 ten-class volume against the per-class loop of the binary entries."""
 import pytest
 import torch

@@ -1,14 +1,13 @@
-// TEST INFRASTRUCTURE: a stand-alone host program that runs segm_ccl_roots_conn and segm_ccl_label_roots_conn (csrc/ccl_conn.hip; at
-// connectivity 1 they forward to csrc/postprocess.hip and csrc/ccl_labels.hip) on the CPU emulation of HIP with every buffer
-// allocated at its exact size, to be built with AddressSanitizer + UBSan: a neighbour index past a buffer - x - 1 at x = 0 of the
-// first row, x + 1 at the end of the last - a misaligned access or an overflow in the index arithmetic is reported.  No Python, no GPU.
+// TEST INFRASTRUCTURE: a stand-alone host program that runs segm_ccl_roots_conn and segm_ccl_label_roots_conn
+// (csrc/ccl_roots.hip) on the CPU emulation of HIP with every buffer allocated at its exact size, to be built with AddressSanitizer +
+// UBSan: a neighbour index past a buffer - x - 1 at x = 0 of the first row, x + 1 at the end of the last - a misaligned access or an
+// overflow in the index arithmetic is reported.  No Python, no GPU.
 //
 //   CXX=/opt/rocm/lib/llvm/bin/clang++
 //   F="-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -pthread -Itests/emu -Wno-unused-value -DSEGM_EMU=1"
 //   $CXX $F '-DSEGM_PIN_F32(x)=' '-DSEGM_SCHED_FENCE()=' '-DSEGM_PIN_F2(x)=' '-DSEGM_WAVE_LDS_SYNC()=hipemu::sync_wave()' \
 //        '-DSEGM_BLOCK_LDS_SYNC()=hipemu::sync_block()' \
-//        -x c++ segmamba_amd/csrc/ccl_conn.hip segmamba_amd/csrc/ccl_labels.hip segmamba_amd/csrc/postprocess.hip \
-//        tests/emu/hip_emu_runtime.cpp tools/ccl_conn_sanitize.cpp -o build/ccl_conn_sanitize
+//        -x c++ segmamba_amd/csrc/ccl_roots.hip tests/emu/hip_emu_runtime.cpp tools/ccl_conn_sanitize.cpp -o build/ccl_conn_sanitize
 //   ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 build/ccl_conn_sanitize
 //
 // Cases, each at connectivity 1, 2 and 3: random masks of density 0.1, 0.3 and 0.6 on the 27 volumes whose sides are 1 below, at and

@@ -1,12 +1,13 @@
-// TEST INFRASTRUCTURE: a stand-alone host program that runs segm_ccl_label_roots and segm_ccl_label_select (csrc/ccl_labels.hip) on the
-// CPU emulation of HIP with every buffer allocated at its exact size, to be built with AddressSanitizer + UBSan: an index past a
-// buffer, a misaligned access or an overflow in the index arithmetic is reported.  No Python, no GPU.
+// TEST INFRASTRUCTURE: a stand-alone host program that runs segm_ccl_label_roots (csrc/ccl_roots.hip) and segm_ccl_label_select
+// (csrc/ccl_labels.hip) on the CPU emulation of HIP with every buffer allocated at its exact size, to be built with AddressSanitizer
+// + UBSan: an index past a buffer, a misaligned access or an overflow in the index arithmetic is reported.  No Python, no GPU.
 //
 //   CXX=/opt/rocm/lib/llvm/bin/clang++
 //   F="-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17 -pthread -Itests/emu -Wno-unused-value -DSEGM_EMU=1"
 //   $CXX $F '-DSEGM_PIN_F32(x)=' '-DSEGM_SCHED_FENCE()=' '-DSEGM_PIN_F2(x)=' '-DSEGM_WAVE_LDS_SYNC()=hipemu::sync_wave()' \
 //        '-DSEGM_BLOCK_LDS_SYNC()=hipemu::sync_block()' \
-//        -x c++ segmamba_amd/csrc/ccl_labels.hip tests/emu/hip_emu_runtime.cpp tools/ccl_labels_sanitize.cpp -o build/ccl_labels_sanitize
+//        -x c++ segmamba_amd/csrc/ccl_roots.hip segmamba_amd/csrc/ccl_labels.hip tests/emu/hip_emu_runtime.cpp tools/ccl_labels_sanitize.cpp \
+//        -o build/ccl_labels_sanitize
 //   ASAN_OPTIONS=detect_leaks=0:detect_stack_use_after_return=0 build/ccl_labels_sanitize
 //
 // Cases: random labels 0 .. 3 in runs of two along x on the 27 volumes whose sides are 1 below, at and 1 above the tile's

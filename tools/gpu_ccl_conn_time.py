@@ -1,12 +1,11 @@
-"""Time the connected components at connectivity 1, 2 and 3 (csrc/ccl_conn.hip) on the synthetic 10-class 200 x 256 x 256 label map of
+"""Time the connected components at connectivity 1, 2 and 3 (csrc/ccl_roots.hip) on the synthetic 10-class 200 x 256 x 256 label map of
 tools/gpu_ccl_labels_time.py.
 
     python tools/gpu_ccl_conn_time.py [--calls 30] [--shape 200 256 256] [--no-scipy] [--out profiles/ccl_conn_time.json]
 
 Timed: `keep_largest_per_class` (all classes, one labelled pass) and `largest_connected_domain` of one organ's mask (label 5), each at
 connectivity 1, 2 and 3.  HIP events around whole calls, the six variants alternating, the median over `--calls` calls after warm-up.
-Yardsticks, neither of them the code under test: the connectivity-1 calls (the kernels of the parent commit; README records 0.270 ms
-for `keep_largest_per_class` there) and, once, `scipy.ndimage.label` with the full structure on the host - the only route to the
+Yardsticks: the connectivity-1 calls (README records 0.270 ms for `keep_largest_per_class` there) and, once, `scipy.ndimage.label` with the full structure on the host - the only route to the
 connectivity-3 result without these kernels.
 Asserted before anything is timed (the tool fails otherwise, and the JSON records them): at every connectivity the label map of
 `keep_largest_per_class` equals the per-class loop over the binary entries, its roots per class equal the binary entry's, two calls
@@ -113,11 +112,8 @@ def main():
 
     # bytes the algorithm needs per launch, from the shapes: the byte volume, int32 labels / roots / sizes, the byte output.  The
     # merge launch reads every voxel's byte once; the up to 13 neighbour bytes of a boundary voxel come from lines already read.
-    nbytes = {"conn_tile_kernel": n + 4 * n, "conn_merge_kernel": n,
-              "lccl_tile_kernel": n + 4 * n, "lccl_merge_kernel": n, "lccl_flatten_kernel": 4 * n + 4 * n, "ccl_sizes_kernel": 4 * n,
-              "label_best_kernel": 4 * n, "label_select_kernel": n + 4 * n + n,
-              "ccl_tile_kernel": n + 4 * n, "ccl_merge_kernel": n, "ccl_flatten_kernel": 4 * n + 4 * n, "ccl_best_kernel": 4 * n,
-              "ccl_select_kernel": 4 * n + n}
+    nbytes = {"roots_tile_kernel": n + 4 * n, "roots_merge_kernel": n, "roots_flatten_kernel": 4 * n + 4 * n, "ccl_sizes_kernel": 4 * n,
+              "label_best_kernel": 4 * n, "label_select_kernel": n + 4 * n + n, "ccl_best_kernel": 4 * n, "ccl_select_kernel": 4 * n + n}
     rec["kernels"] = {}
     variants = [(f"keep_largest_per_class_c{c}", fns[i]) for i, c in enumerate(conns)] \
         + [(f"largest_connected_domain_c{c}", fns[3 + i]) for i, c in enumerate(conns)]

@@ -1,5 +1,5 @@
-"""Time `keep_largest_per_class` (one labelled connected-components pass, csrc/ccl_labels.hip) against the per-class loop over the
-binary entries that gives the same label map, on a synthetic 10-class 200 x 256 x 256 volume.
+"""Time `keep_largest_per_class` (one labelled connected-components pass, csrc/ccl_roots.hip and ccl_labels.hip) against the per-class
+loop over the binary entries that gives the same label map, on a synthetic 10-class 200 x 256 x 256 volume.
 
     python tools/gpu_ccl_labels_time.py [--calls 30] [--shape 200 256 256] [--out profiles/ccl_labels_time.json]
 
@@ -87,10 +87,8 @@ def main():
     rec["loop_over_one_pass"] = rec["per_class_loop"]["ms_median"] / rec["keep_largest_per_class"]["ms_median"]
 
     # bytes the algorithm needs per launch, from the shapes: label bytes, int32 labels / roots / sizes, the byte output
-    nbytes = {"lccl_tile_kernel": n + 4 * n, "lccl_merge_kernel": n, "lccl_flatten_kernel": 4 * n + 4 * n, "ccl_sizes_kernel": 4 * n,
-              "label_best_kernel": 4 * n, "label_select_kernel": n + 4 * n + n,
-              "ccl_tile_kernel": n + 4 * n, "ccl_merge_kernel": n, "ccl_flatten_kernel": 4 * n + 4 * n, "ccl_best_kernel": 4 * n,
-              "ccl_select_kernel": 4 * n + n}
+    nbytes = {"roots_tile_kernel": n + 4 * n, "roots_merge_kernel": n, "roots_flatten_kernel": 4 * n + 4 * n, "ccl_sizes_kernel": 4 * n,
+              "label_best_kernel": 4 * n, "label_select_kernel": n + 4 * n + n, "ccl_best_kernel": 4 * n, "ccl_select_kernel": 4 * n + n}
     rec["kernels"] = {}
     for what, fn in (("keep_largest_per_class", one_pass), ("per_class_loop", loop)):
         try:
@@ -103,7 +101,7 @@ def main():
         for kname, (cnt, us) in sorted(split.items(), key=lambda kv: -kv[1][1]):
             row = {"calls": cnt, "us_per_call": us / cnt}
             for key, b in nbytes.items():
-                if "::" + key in kname or kname.startswith(key):      # not a substring test: lccl_tile_kernel holds ccl_tile_kernel
+                if "::" + key in kname or kname.startswith(key):
                     row["bytes_per_call_by_count"] = b
                     row["TB_per_s"] = b / (us / cnt * 1e-6) / 1e12
             out["by_kernel"][kname] = row

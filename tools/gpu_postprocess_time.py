@@ -127,7 +127,7 @@ def main():
 
     # (c) per kernel
     t = torch.from_numpy(masks["pred_WT"]).cuda()
-    nbytes = {"ccl_tile_kernel": n + 4 * n, "ccl_merge_kernel": n, "ccl_flatten_kernel": 4 * n + 4 * n, "ccl_sizes_kernel": 4 * n,
+    nbytes = {"roots_tile_kernel": n + 4 * n, "roots_merge_kernel": n, "roots_flatten_kernel": 4 * n + 4 * n, "ccl_sizes_kernel": 4 * n,
               "ccl_best_kernel": 4 * n, "ccl_select_kernel": 4 * n + n, "resample_argmax_kernel": 4 * 4 * n + n}
     logits = logits_for(pred, SHAPE)
     calls_of = {"largest_connected_domain": lambda: PP.largest_connected_domain(t), "labels_from_logits": lambda: PP.labels_from_logits(logits)}
