@@ -1,33 +1,23 @@
-"""Dense 3x3x3 (stride 1, "same") convolutions of the SegMamba stem: a dispatcher over the library's own MFMA kernels and
-the vendor routes - by a shape table since round 3 (`_table_choice`), by a timing run on request (SEGM_CONV_AUTOTUNE=1).
+"""Dense 3x3x3 (stride 1, "same") convolutions of the SegMamba stem: forward, data gradient and weight gradient, each routed
+by one table of the shape to one of the library's own MFMA kernels or to the vendor (MIOpen) call.
 
-SURVEY.md §7 step 6: the stem started on MIOpen.  Profiling (profiles/r01_probe_convs.log,
-profiles/r01_bench_step_kernels_v3.txt) showed that MIOpen's bf16 3-D solvers are very uneven on these shapes:
+Every call is mathematically the same convolution, whichever route it takes:
 
-  * forward at 48 channels runs at 200-260 TF/s, but 96 -> 96 @64^3 only at 54 TF/s;
-  * backward-data for 48 -> 48 @128^3 takes 12.5 ms while the *forward* kernel on the same shape takes 2.5 ms;
-  * one layer (decoder2.conv1, 96 -> 48 @128^3) picks solvers that need 75 ms (data) + 530 ms (weights) - more than
-    half of a whole training step.
+  fwd    y  = conv(x, W)                      F.conv3d
+                                              or  segm_conv3d_k3_fwd, the row kernels, per 48-channel input block (csrc/conv3d_fwd.hip)
+                                              or  segm_conv3d_k3_cube_fwd, the whole contraction in one launch (csrc/conv3d_cube.hip)
+  dgrad  dx = conv_bwd_data(dy, W)            the vendor call, or the same two forward kernels on dy with flip(W)^T
+  wgrad  dW = conv_bwd_weight(x, dy)          the vendor call, segm_conv3d_k3_wgrad ("mfma") or segm_conv3d_k3_cube_wgrad
 
-Every quantity below is mathematically the same convolution, only routed to a different library call:
-
-  fwd    y  = conv(x, W)                      or  sum over 48-channel input blocks / concat over output blocks
-                                              or  segm_conv3d_k3_fwd, the library's own NCDHW MFMA kernel (per 48-channel
-                                                  input block; csrc/conv3d_fwd.hip)
-  dgrad  dx = conv_bwd_data(dy, W)            or  conv(dy, flip(W)^T)         (a forward convolution, any of the above)
-  wgrad  dW = conv_bwd_weight(x, dy)          or  per input/output channel block
-                                              or  segm_conv3d_k3_wgrad, the library's own MFMA kernel
-
-Rounds 1 - 2 timed every candidate the first time a (kind, shapes, dtype, device, strides) was seen and cached the fastest
-(what MIOpen's own "find" does, one level up).  The winners were the same on every box (profiles/r01_conv_autotune_v2.log,
-r02_bench_variants.log): the library's kernels for every layer of width >= 16, the vendor GEMM route for the 8^3 bottleneck
-layers.  That outcome is now the routing table; with SEGM_CONV_AUTOTUNE=1 the timing run is back (SEGM_CONV_VERBOSE=1 prints
-its timings).
+A call lists the variants that apply to its operands (`_fwd_variants`, `_wgrad_variants`: the vendor route first), `_route` picks
+one of them through `_table_choice`, and `_run_fwd` / `_run_wgrad` launch it.  The choice is a pure function of the shape, so every
+rank, every run and every captured graph takes the same kernels.  Why MIOpen does not serve these shapes, and the timing runs the
+table was frozen from: docs/history/, profiles/r01_probe_convs.log, r02_bench_variants.log, r03_conv_tuner_vs_table.log.
 """
 from __future__ import annotations
 
 import os
-from typing import Callable, Dict, List, Tuple
+from typing import List, Tuple
 
 import torch
 import torch.nn.functional as F
@@ -35,54 +25,26 @@ import torch.nn.functional as F
 from . import linear
 
 _BLOCK = 48                      # channel block of the library's kernels (and of MIOpen's fast 3-D bf16 solvers)
-_cache: Dict[tuple, int] = {}
-# Routing is a TABLE by default (round 3): the winners of the round-2 timing runs as a rule of the shape (`_table_choice`), so that
-# every rank, every run and every captured graph takes the same kernels and results are reproducible run to run.
-# SEGM_CONV_AUTOTUNE=1 brings the timing-based choice back (to re-derive the table on new hardware; it synchronises the device
-# inside autograd, may differ between processes, and cannot run under graph capture).
-_TUNE = os.environ.get("SEGM_CONV_AUTOTUNE", "0") == "1"
-# cat(up, skip) convolutions as one autograd node with the later parts added in place (_ConvSameCat, linear._PointwiseCat).  Timed in
-# round 3: no gain on the MI355X (66.2 ms per step either way), so it stays opt-in.
-_CAT_FUSED = os.environ.get("SEGM_CONV_CAT_FUSED", "1") == "1"     # round 5: default on (with the statistics epilogue the cat layers feed their InstanceNorm too; profiles/r05_inorm_epilogue_step.log)
-# round 5: the chained kernels' storing K part sums {count, y, y^2} of what it writes; the InstanceNorm behind the convolution
-# merges those partials instead of reading the volume again (csrc/conv3d_fwd.hip STATS; measured free on the convolution side,
+# cat(up, skip) convolutions as one autograd node with the later parts added in place (_ConvSameCat, linear._PointwiseCat): with the
+# statistics epilogue the cat layers feed their InstanceNorm too (profiles/r05_inorm_epilogue_step.log).  SEGM_CONV_CAT_FUSED=0: one
+# node per part.
+_CAT_FUSED = os.environ.get("SEGM_CONV_CAT_FUSED", "1") == "1"
+# the chained row kernels and the cube kernel store K part sums {count, y, y^2} of what they write; the InstanceNorm behind the
+# convolution merges those partials instead of reading the volume again (csrc/conv3d_fwd.hip STATS; free on the convolution side,
 # profiles/r05_inorm_epilogue.log).  SEGM_CONV_STATS=0: every InstanceNorm makes its own statistics pass (A/B).
 _STATS = os.environ.get("SEGM_CONV_STATS", "1") == "1"
-# round 5: conv1 + the 1x1x1 projection of a residual block's input as one node (_ResFront): the two data gradients of the input are
-# summed by the 3x3x3 kernel's accumulate mode instead of an element-wise add.  SEGM_RES_FRONT=0: two nodes (A/B).
+# conv1 + the 1x1x1 projection of a residual block's input as one node (_ResFront): the two data gradients of the input are summed
+# by the 3x3x3 kernel's accumulate mode instead of an element-wise add.  SEGM_RES_FRONT=0: two nodes (A/B).
 _RES_FRONT = os.environ.get("SEGM_RES_FRONT", "1") == "1"
-
-
-# round 6 (late): the wide layers of the 8^3 / 16^3 / 32^3 levels on segm_conv3d_k3_cube_fwd (csrc/conv3d_cube.hip) - forward and data
-# gradient; 2.5 - 6x over the row kernels / the vendor route there (profiles/r06_conv_cube_v2.txt).  SEGM_CONV_CUBE=0: the round-5 routing.
+# the wide layers of the 8^3 / 16^3 / 32^3 levels on segm_conv3d_k3_cube_fwd - forward and data gradient; 2.5 - 6x over the row
+# kernels / the vendor route there (profiles/r06_conv_cube_v2.txt).  SEGM_CONV_CUBE=0: row kernels and the vendor route only.
 _CUBE = os.environ.get("SEGM_CONV_CUBE", "1") == "1"
 _CUBE_MAX_WIDTH = int(os.environ.get("SEGM_CONV_CUBE_MAX_WIDTH", "32"))
 # ... and the weight gradients of the 8^3 level and of the 384-channel layers at 16^3 on segm_conv3d_k3_cube_wgrad (dY cube and X halo
-# cube in LDS, a wave = a 16 x 16 (co, ci) tile x 27 taps): 2.1 - 2.6x over the vendor route at 8^3 - the last MIOpen convolution of the
-# step -, 1.7 - 1.8x over the row kernel at 384 -> 384 @16^3; behind it below 384 channels and at 32^3 (profiles/r06_conv_cube_wgrad_v5.txt)
+# cube in LDS, a wave = a 16 x 16 (co, ci) tile x 27 taps): 2.1 - 2.6x over the vendor route at 8^3, 1.7 - 1.8x over the row kernel at
+# 384 -> 384 @16^3; behind it below 384 channels and at 32^3 (profiles/r06_conv_cube_wgrad_v5.txt)
 _CUBE_WGRAD = os.environ.get("SEGM_CONV_CUBE_WGRAD", "1") == "1"
 _CUBE_WGRAD_MAX_WIDTH = int(os.environ.get("SEGM_CONV_CUBE_WGRAD_MAX_WIDTH", "16"))
-
-
-def _time(fn: Callable[[], torch.Tensor], reps: int = 3) -> float:
-    """median of `reps` timed calls after one warm-up call (close candidates differ by a few per cent)"""
-    fn()
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(reps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    return sorted(times)[len(times) // 2]
-
-
-def _key(kind, x, w, *flags) -> tuple:
-    """cache key of one routing decision: everything a candidate's speed (or applicability) depends on - shapes, dtype,
-    the device, and the operand strides (NCDHW vs channels-last views take different MIOpen solvers)"""
-    return (kind, tuple(x.shape), tuple(w.shape), x.dtype, x.device.index, tuple(x.stride()), tuple(w.stride())) + flags
 
 
 def _table_variant(width: int):
@@ -120,41 +82,16 @@ def _table_choice(kind: str, width: int, variants) -> int:
     return 0
 
 
-def _pick(key: tuple, cands: List[Callable[[], torch.Tensor]], variants=None, width: int = 0, box: list = None) -> torch.Tensor:
-    """`box`: the statistics the candidates append to - emptied before the launch whose result is returned, so that what it
-    holds afterwards belongs to that launch and not to a timed candidate"""
-    if len(cands) == 1 or not torch.cuda.is_available():
-        return cands[0]()
-    if not _TUNE:
-        return cands[_table_choice(key[0], width, variants) if variants is not None else 0]()
-    i = _cache.get(key)
-    if i is None:
-        times = []
-        for c in cands:
-            try:
-                times.append(_time(c))
-            except RuntimeError as e:
-                # only "this candidate does not take this shape" is a score (the library's status -2 / -4, MIOpen's
-                # "no solver"); a HIP launch failure or an out-of-memory error must surface, not be timed as infinity
-                msg = str(e)
-                if "HIP error" in msg or "out of memory" in msg:
-                    raise
-                times.append(float("inf"))
-        i = min(range(len(cands)), key=lambda j: times[j])
-        _cache[key] = i
-        if os.environ.get("SEGM_CONV_VERBOSE"):
-            print(f"[conv3d autotune] {key}: " + ", ".join(f"{t:.2f} ms" for t in times) + f" -> {i}", flush=True)
-    if box is not None:
-        box.clear()
-    return cands[i]()
+def _route(kind: str, width: int, variants):
+    """the variant this call takes: the table's choice among `variants`; the vendor route where nothing else applies or there is
+    no device.  The one place a route is decided (tests force a route by replacing this function)."""
+    if len(variants) == 1 or not torch.cuda.is_available():
+        return variants[0]
+    return variants[_table_choice(kind, width, variants)]
 
 
 def _blocks(c: int) -> List[slice]:
     return [slice(i, min(i + _BLOCK, c)) for i in range(0, c, _BLOCK)]
-
-
-def _fwd_native(x, w, pad):
-    return F.conv3d(x, w, None, 1, pad)
 
 
 def _hip_fwd_ok(x, w) -> bool:
@@ -208,13 +145,10 @@ def _fwd_hip(x, w, pad, bias=None, chain=False, pitch48=False, chain32=False, in
 
 def _cube_ok(x, cout: int, cin_w: int) -> bool:
     """the cube kernel takes this convolution AND the table prefers it: every supported layer of width <= 16, at 32^3 the layers from
-    96 -> 192 channels up (96 -> 96 is level with the row kernel, which also carries the statistics epilogue); with the tuner on,
-    wherever it is supported"""
+    96 -> 192 channels up (96 -> 96 is level with the row kernel, which also carries the statistics epilogue)"""
     from . import ops_raw
     if not _CUBE or not ops_raw.conv3d_cube_supported(x, cout) or x.shape[1] != cin_w:
         return False
-    if _TUNE:
-        return True
     width = x.shape[4]
     return width <= min(16, _CUBE_MAX_WIDTH) or (width <= _CUBE_MAX_WIDTH and width <= 32 and x.shape[1] * cout >= 96 * 192)
 
@@ -238,55 +172,10 @@ def _fwd_cube(x, w, bias=None, into=None, flipped=False, stats_box=None):
     return res
 
 
-def _fwd_lib(v, x, w, pad, bias=None, into=None, stats_box=None, flipped=False):
-    """the library kernel variant `v` (a row-kernel flag tuple or "cube") on one part of a convolution"""
-    if v == "cube":
-        return _fwd_cube(x, w, bias, into=into, flipped=flipped, stats_box=stats_box)
-    return _fwd_hip(x, w, pad, bias, *v, into=into, flipped=flipped, stats_box=stats_box)
-
-
-def _hip_chain_ok(w) -> bool:
-    """The chained-K-parts kernel (eight-wave layout) as an extra autotune candidate: on MI355X it beats the
-    reduce-per-row kernel by 5 - 16 % on the 128^3 / 64^3 layers and loses ~4 % at 32^3 (profiles/r01_conv_chain_ab.log), so the
-    tuner decides per shape.  SEGM_CONV_FWD_CHAIN=0 removes the candidate."""
-    return w.shape[0] % _BLOCK == 0 and os.environ.get("SEGM_CONV_FWD_CHAIN", "1") != "0"
-
-
-def _hip_untimed_ok() -> bool:
-    """Two further variants of the chained kernel - unpadded LDS rows, 32-wide x blocks with two workgroups per CU.  Measured in
-    round 2 (profiles/r02_bench_variants.log): the 32-wide variant wins every 32^3 / 16^3 layer (96 -> 96 @32^3 0.15 -> 0.11 ms,
-    192 -> 192 @32^3 0.43 -> 0.27 ms, 384 -> 384 @16^3 0.41 -> 0.31 ms, where MIOpen was the previous winner) and the step drops from
-    79.2 to 77.9 ms, so both are candidates by default; SEGM_CONV_FWD_UNTIMED=0 removes them."""
-    return os.environ.get("SEGM_CONV_FWD_UNTIMED", "1") == "1"
-
-
-def _fwd_blocked(x, w, pad):
-    outs = []
-    for ob in _blocks(w.shape[0]):
-        acc = None
-        for ib in _blocks(w.shape[1]):
-            y = F.conv3d(x[:, ib], w[ob, ib], None, 1, pad)
-            acc = y if acc is None else acc + y
-        outs.append(acc)
-    return outs[0] if len(outs) == 1 else torch.cat(outs, dim=1)
-
-
 def _dgrad_native(dy, w, x, pad):
     return torch.ops.aten.convolution_backward(dy, x, w, None,
                                                 [1, 1, 1], [pad] * 3, [1, 1, 1], False, [0, 0, 0], 1,
                                                 [True, False, False])[0]
-
-
-def _flipT(w):
-    return w.flip(2, 3, 4).transpose(0, 1).contiguous()
-
-
-def _dgrad_as_fwd(dy, w, x, pad):
-    return F.conv3d(dy, _flipT(w), None, 1, pad)                 # valid for stride 1 and pad == k // 2
-
-
-def _dgrad_as_fwd_blocked(dy, w, x, pad):
-    return _fwd_blocked(dy, _flipT(w), pad)
 
 
 def _dgrad_hip(dy, w, x, pad, chain=False, pitch48=False, chain32=False, into=None):
@@ -299,14 +188,6 @@ def _wgrad_native(x, dy, w, pad):
                                                 [False, True, False])[1]
 
 
-def _wgrad_blocked(x, dy, w, pad):
-    dw = torch.empty_like(w, memory_format=torch.contiguous_format)
-    for ob in _blocks(w.shape[0]):
-        for ib in _blocks(w.shape[1]):
-            dw[ob, ib] = _wgrad_native(x[:, ib].contiguous(), dy[:, ob].contiguous(), w[ob, ib].contiguous(), pad)
-    return dw
-
-
 def _wgrad_mfma(x, dy, w, pad, out_dtype=None):
     """segm_conv3d_k3_wgrad: the hand-written MFMA weight-gradient kernel (csrc/conv3d_wgrad.hip); the result in the dtype
     of the master weight (fp32 under autocast: the kernel's accumulators, not rounded)."""
@@ -317,13 +198,10 @@ def _wgrad_mfma(x, dy, w, pad, out_dtype=None):
 
 
 def _cube_wgrad_ok(x, dy, w) -> bool:
-    """segm_conv3d_k3_cube_wgrad takes the layer AND the table prefers it (8^3: every wide layer; 16^3: from 384 x 384 channels; with
-    the tuner on, wherever it is supported)"""
+    """segm_conv3d_k3_cube_wgrad takes the layer AND the table prefers it (8^3: every wide layer; 16^3: from 384 x 384 channels)"""
     from . import ops_raw
     if not _CUBE_WGRAD or w.shape[2:] != (3, 3, 3) or not ops_raw.conv3d_cube_wgrad_supported(x, dy):
         return False
-    if _TUNE:
-        return True
     width, prod = x.shape[4], x.shape[1] * dy.shape[1]
     return width <= _CUBE_WGRAD_MAX_WIDTH and ((width <= 8 and prod >= 96 * 192) or (width <= 16 and prod >= 384 * 384))
 
@@ -345,91 +223,71 @@ def _mfma_wgrad_ok(x, dy, w) -> bool:
 _HIP_VARIANTS = ((False, False, False), (True, False, False), (True, True, False), (False, False, True))   # (chain, pitch48, chain32)
 
 
-def _fwd_candidates(x, w, bias, pad, stats_box=None):
-    """-> (key, candidates, variant per candidate): the mathematically identical routings of one forward convolution; variant =
-    the library kernel's (chain, pitch48, chain32) flags, None for the vendor routes"""
-    hip = _hip_fwd_ok(x, w)
-    chain = hip and _hip_chain_ok(w)
-    key = _key("fwd", x, w, hip, chain, _hip_untimed_ok(), _CUBE)
-
-    def with_bias(y):
-        return y if bias is None else y + bias.view(1, -1, 1, 1, 1)
-
-    cands, variants = [lambda: F.conv3d(x, w, bias, 1, pad)], [None]
-    if max(w.shape[0], w.shape[1]) > _BLOCK and w.shape[0] % _BLOCK == 0 and w.shape[1] % _BLOCK == 0:
-        cands.append(lambda: with_bias(_fwd_blocked(x, w, pad)))
-        variants.append(None)
-    n = (1 if hip else 0) + (1 if chain else 0) + (2 if chain and _hip_untimed_ok() else 0)
-    for v in _HIP_VARIANTS[:n]:                          # bias fused into the kernel's epilogue
-        cands.append(lambda v=v: _fwd_hip(x, w, pad, bias, *v, stats_box=stats_box))
-        variants.append(v)
+def _fwd_variants(x, w, flipped=False) -> list:
+    """the routes that apply to the forward convolution of x with w, the table's preference aside: None (the vendor call), the row
+    kernels' flag tuples (the chained ones need Cout % 48 == 0), "cube" where `_cube_ok`.  `flipped`: the data gradient - x is the
+    output gradient, w the forward weight."""
+    if flipped:
+        w = w.transpose(0, 1)
+    variants = [None]
+    if _hip_fwd_ok(x, w):
+        variants += _HIP_VARIANTS if w.shape[0] % _BLOCK == 0 else _HIP_VARIANTS[:1]
     if w.shape[2:] == (3, 3, 3) and w.dtype == x.dtype and _cube_ok(x, w.shape[0], w.shape[1]):
-        cands.append(lambda: _fwd_cube(x, w, bias, stats_box=stats_box))
         variants.append("cube")
-    return key, cands, variants
+    return variants
 
 
-def _pick_was_hip(key, cands, variants, width: int = 0) -> bool:
-    """did `_pick` return the result of a library-kernel candidate (only then are statistics in the box those of the result)"""
-    if len(cands) == 1 or not torch.cuda.is_available():
-        return _is_lib(variants[0])
-    if not _TUNE:
-        return _is_lib(variants[_table_choice(key[0], width, variants)])
-    i = _cache.get(key)
-    return i is not None and _is_lib(variants[i])
+def _wgrad_variants(x, dy, w) -> list:
+    """the routes that apply to the weight gradient: None (the vendor call), "mfma", "cube" where `_cube_wgrad_ok`"""
+    variants = [None]
+    if _mfma_wgrad_ok(x, dy, w):
+        variants.append("mfma")
+    if _cube_wgrad_ok(x, dy, w):
+        variants.append("cube")
+    return variants
 
 
-def _tuned_variant(key, cands, variants, width: int = 0):
-    """the library-kernel variant routing gives this key (table, or what the tuner has already picked), or None (a vendor route)"""
-    if len(cands) == 1 or not torch.cuda.is_available():
-        return None
-    if not _TUNE:
-        v = variants[_table_choice(key[0], width, variants)]
-        return v if _is_lib(v) else None
-    i = _cache.get(key)
-    return variants[i] if i is not None and _is_lib(variants[i]) else None
+def _run_fwd(v, x, w, pad, bias=None, into=None, stats_box=None, flipped=False, like=None):
+    """route `v` on one part of a convolution.  `into` (library kernels): an existing result the launch adds to; `stats_box`: see
+    `_fwd_hip`; `flipped`: the data gradient - x is the output gradient, w the forward weight and `like` the convolution's input,
+    whose shape the vendor call wants."""
+    if v == "cube":
+        return _fwd_cube(x, w, bias, into=into, flipped=flipped, stats_box=stats_box)
+    if v is not None:
+        return _fwd_hip(x, w, pad, bias, *v, into=into, flipped=flipped, stats_box=stats_box)
+    assert into is None
+    return _dgrad_native(x, w, like, pad) if flipped else F.conv3d(x, w, bias, 1, pad)
+
+
+def _add_part(into, v, x, w, pad, stats_box=None, flipped=False, like=None):
+    """into += the convolution `_run_fwd(v, x, w, ...)` computes (the next part of a concatenated input; a second gradient of the
+    same tensor): by the library kernel's accumulate mode where it has one for this shape (Cout % 48 == 0; a data gradient's target
+    with dense channels), by an ordinary add otherwise"""
+    from . import ops_raw
+    cout = w.shape[1] if flipped else w.shape[0]
+    if _is_lib(v) and cout % _BLOCK == 0 and (not flipped or ops_raw.channel_dense(into)):
+        return _run_fwd(v, x, w, pad, into=into, stats_box=stats_box, flipped=flipped)
+    return into.add_(_run_fwd(v, x, w, pad, flipped=flipped, like=like))
+
+
+def _run_wgrad(v, x, dy, w, pad, w_dtype):
+    if v == "cube":
+        return _wgrad_cube(x, dy, w_dtype)
+    if v == "mfma":
+        return _wgrad_mfma(x, dy, w, pad, w_dtype)
+    return _wgrad_native(x, dy, w, pad)
 
 
 def _dgrad(dy, w, x, pad, into=None):
-    """`into`: a gradient of x that already exists (another consumer's, owned by the caller) - the result is added to it, in place
-    by the library kernel when the shape routes to one (`accumulate`), by an ordinary add otherwise"""
-    cands, variants = [lambda: _dgrad_native(dy, w, x, pad), lambda: _dgrad_as_fwd(dy, w, x, pad)], [None, None]
-    if max(w.shape[0], w.shape[1]) > _BLOCK and w.shape[0] % _BLOCK == 0 and w.shape[1] % _BLOCK == 0:
-        cands.append(lambda: _dgrad_as_fwd_blocked(dy, w, x, pad))
-        variants.append(None)
-    hip = _hip_fwd_ok(dy, w.transpose(0, 1))
-    chain = hip and _hip_chain_ok(w.transpose(0, 1))
-    n = (1 if hip else 0) + (1 if chain else 0) + (2 if chain and _hip_untimed_ok() else 0)
-    for v in _HIP_VARIANTS[:n]:
-        cands.append(lambda v=v: _dgrad_hip(dy, w, x, pad, *v))
-        variants.append(v)
-    if w.shape[2:] == (3, 3, 3) and w.dtype == dy.dtype and _cube_ok(dy, w.shape[1], w.shape[0]):
-        cands.append(lambda: _fwd_cube(dy, w, flipped=True))
-        variants.append("cube")
-    key = _key("dgrad", dy, w, hip, chain, _hip_untimed_ok(), _CUBE)
+    """`into`: a gradient of x that already exists (another consumer's, owned by the caller) - the result is added to it"""
+    v = _route("dgrad", dy.shape[4], _fwd_variants(dy, w, flipped=True))
     if into is not None:
-        from . import ops_raw
-        v = _tuned_variant(key, cands, variants, dy.shape[4]) if w.shape[1] % _BLOCK == 0 and ops_raw.channel_dense(into) else None
-        if v is not None:
-            return _fwd_lib(v, dy, w, pad, into=into, flipped=True)
-        return into.add_(_pick(key, cands, variants, dy.shape[4]))
-    return _pick(key, cands, variants, dy.shape[4])
+        return _add_part(into, v, dy, w, pad, flipped=True, like=x)
+    return _run_fwd(v, dy, w, pad, flipped=True, like=x)
 
 
 def _wgrad(x, dy, w, pad, w_dtype):
-    cands, variants = [lambda: _wgrad_native(x, dy, w, pad)], [None]
-    if max(w.shape[0], w.shape[1]) > _BLOCK and w.shape[0] % _BLOCK == 0 and w.shape[1] % _BLOCK == 0:
-        cands.append(lambda: _wgrad_blocked(x, dy, w, pad))
-        variants.append(None)
-    mfma = _mfma_wgrad_ok(x, dy, w)
-    if mfma:
-        cands.append(lambda: _wgrad_mfma(x, dy, w, pad, w_dtype))
-        variants.append("mfma")
-    cube = _cube_wgrad_ok(x, dy, w)
-    if cube:
-        cands.append(lambda: _wgrad_cube(x, dy, w_dtype))
-        variants.append("cube")
-    return _pick(_key("wgrad", x, w, mfma, w_dtype, cube), cands, variants, x.shape[4]).to(w_dtype)
+    return _run_wgrad(_route("wgrad", x.shape[4], _wgrad_variants(x, dy, w)), x, dy, w, pad, w_dtype).to(w_dtype)
 
 
 class _ConvSame(torch.autograd.Function):
@@ -441,14 +299,11 @@ class _ConvSame(torch.autograd.Function):
         w, bias = _masters(ctx, x, w, bias)              # fp32 masters -> the step's 16-bit copies; gradients go back in fp32
         ctx.save_for_backward(x, w)
         box = [] if want_stats else None
-        key, cands, variants = _fwd_candidates(x, w, bias, w.shape[2] // 2, box)
-        out = _pick(key, cands, variants, x.shape[4], box)
+        out = _run_fwd(_route("fwd", x.shape[4], _fwd_variants(x, w)), x, w, w.shape[2] // 2, bias, stats_box=box)
         ctx.with_stats = bool(want_stats)
         if not want_stats:
             return out
-        # the tuner empties the box before the launch whose result is returned: what it holds now came from that launch (and a
-        # winning variant without the statistics epilogue leaves it empty)
-        stats = box[-1] if box and _pick_was_hip(key, cands, variants, x.shape[4]) else out.new_empty(0, dtype=torch.float32)
+        stats = box[-1] if box else out.new_empty(0, dtype=torch.float32)      # a launch without the epilogue leaves the box empty
         ctx.mark_non_differentiable(stats)
         return out, stats
 
@@ -471,8 +326,8 @@ class _ConvSame(torch.autograd.Function):
 
 class _ConvSameCat(torch.autograd.Function):
     """conv3d_same(cat(xs, 1), w) without the concatenation AND without the adds: the convolution is linear in its input
-    channels; the first part is a plain convolution with w[:, :c0], every later part is added in place by the library kernel the
-    tuner picked for its shape (`accumulate`) - or, when a vendor route won for that shape, through an ordinary add.  One node
+    channels; the first part is a plain convolution with w[:, :c0], every later part is added in place by the library kernel its
+    shape routes to (`accumulate`) - or, where it routes to the vendor call, through an ordinary add (`_add_part`).  One node
     for the whole layer: the weight gradient is assembled by one cat instead of autograd's zero-fill + copy + add per slice."""
 
     @staticmethod
@@ -486,17 +341,13 @@ class _ConvSameCat(torch.autograd.Function):
         for j, x in enumerate(xs):
             wi = w[:, c0:c0 + x.shape[1]]
             c0 += x.shape[1]
-            key, cands, variants = _fwd_candidates(x, wi, None, pad)
+            v = _route("fwd", x.shape[4], _fwd_variants(x, wi))
             if out is None:
-                out = _pick(key, cands, variants, x.shape[4])
+                out = _run_fwd(v, x, wi, pad)
                 continue
-            v = _tuned_variant(key, cands, variants, x.shape[4]) if wi.shape[0] % _BLOCK == 0 else None
-            if v is not None:
-                box = [] if (want_stats and j + 1 == len(xs)) else None      # the launch that stores the finished values
-                out = _fwd_lib(v, x, wi, pad, into=out, stats_box=box)
-                stats = box[-1] if box else None
-            else:                                        # not tuned yet (this call does it) or a vendor route won
-                out = out + _pick(key, cands, variants, x.shape[4])
+            box = [] if (want_stats and j + 1 == len(xs)) else None          # the launch that stores the finished values
+            out = _add_part(out, v, x, wi, pad, stats_box=box)
+            stats = box[-1] if box else None
         if not want_stats:
             return out
         stats = stats if stats is not None else out.new_empty(0, dtype=torch.float32)
@@ -541,26 +392,18 @@ class _ResFront(torch.autograd.Function):
             c1 = c0 + x.shape[1]
             w1i, w3i, xf = w1[:, c0:c1], w3[:, c0:c1], x.flatten(2)
             c0 = c1
-            last = want_stats and j + 1 == len(xs)
-            box = [] if last else None
+            box = [] if (want_stats and j + 1 == len(xs)) else None          # the launch that stores the finished values
+            v = _route("fwd", x.shape[4], _fwd_variants(x, w1i))
             if y1 is None:
-                key, cands, variants = _fwd_candidates(x, w1i, None, pad, box)
-                y1 = _pick(key, cands, variants, x.shape[4], box)
-                if last and box and _pick_was_hip(key, cands, variants, x.shape[4]):
-                    stats = box[-1]
+                y1 = _run_fwd(v, x, w1i, pad, stats_box=box)
                 y3 = linear._pw_hip(w3i, xf, None)
                 if y3 is None:
                     y3 = linear._bmm_w(w3i, xf)
-                continue
-            key, cands, variants = _fwd_candidates(x, w1i, None, pad)
-            v = _tuned_variant(key, cands, variants, x.shape[4]) if w1i.shape[0] % _BLOCK == 0 else None
-            if v is not None:
-                y1 = _fwd_lib(v, x, w1i, pad, into=y1, stats_box=box)
-                stats = box[-1] if box else None
             else:
-                y1 = y1 + _pick(key, cands, variants, x.shape[4])
-            y = linear._pw_hip(w3i, xf, None, into=y3)
-            y3 = y if y is not None else y3 + linear._bmm_w(w3i, xf)
+                y1 = _add_part(y1, v, x, w1i, pad, stats_box=box)
+                y = linear._pw_hip(w3i, xf, None, into=y3)
+                y3 = y if y is not None else y3 + linear._bmm_w(w3i, xf)
+            stats = box[-1] if box else None
         stats = stats if stats is not None else y1.new_empty(0, dtype=torch.float32)
         ctx.mark_non_differentiable(stats)
         return y1, stats, y3.view(y1.shape)

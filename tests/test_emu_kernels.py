@@ -324,7 +324,7 @@ def test_unet_res_block_on_padded_volumes_emulated(emu, monkeypatch):
     from segmamba_amd import lib as L, unet_blocks as UB, conv3d as C3
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())     # the library's candidates (forward, dgrad, wgrad)
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])     # the library's candidates (forward, dgrad, wgrad)
     torch.manual_seed(3)
     blk = UB.UnetResBlock(96, 48).bfloat16()
     g = torch.Generator().manual_seed(9)
@@ -350,7 +350,7 @@ def test_first_layer_takes_the_thin_input_kernels_emulated(emu, monkeypatch):
     from segmamba_amd import lib as L, unet_blocks as UB, conv3d as C3, fused_norm as FN
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])
     torch.manual_seed(5)
     blk = UB.UnetResBlock(4, 48)
     g = torch.Generator().manual_seed(6)
@@ -788,7 +788,7 @@ def test_conv_dispatcher_library_routes_on_emulated_kernels(emu, monkeypatch):
     xr = x.float().requires_grad_()
     ref = torch.nn.functional.conv3d(xr, w.float(), bias.float(), 1, 1)
     ref.backward(dy.float())
-    assert C3._hip_fwd_ok(x, w) and C3._hip_chain_ok(w)
+    assert C3._hip_fwd_ok(x, w) and C3._fwd_variants(x, w)[1:5] == list(C3._HIP_VARIANTS)      # the chained kernels too
     for chain, p48, c32 in ((False, False, False), (True, False, False), (True, True, False), (False, False, True)):
         y = C3._fwd_hip(x, w, 1, bias, chain, p48, c32)
         assert (y.float() - ref.detach()).abs().max() <= 2e-2 * max(1.0, float(ref.abs().max()))
@@ -1023,7 +1023,6 @@ def test_conv_same_autograd_with_every_library_candidate_on_emulated_kernels(emu
     candidates forced in turn - the CPU twin of tests/test_gpu_kernels.py::test_conv3d_same_autograd_with_library_kernels."""
     from segmamba_amd import conv3d as C3
     monkeypatch.setattr(L, "_lib", emu)
-    monkeypatch.setenv("SEGM_CONV_FWD_UNTIMED", "1")
     g = torch.Generator().manual_seed(4)
     x = torch.randn(1, 48, 2, 4, 16, generator=g).bfloat16().requires_grad_()
     w = (0.05 * torch.randn(48, 48, 3, 3, 3, generator=g)).bfloat16().requires_grad_()
@@ -1033,7 +1032,8 @@ def test_conv_same_autograd_with_every_library_candidate_on_emulated_kernels(emu
     want = torch.autograd.grad(torch.nn.functional.conv3d(x2, w2, b2, 1, 1), (x2, w2, b2), dy.float())
     y_want = torch.nn.functional.conv3d(x2, w2, b2, 1, 1).detach()
     for idx in (-1, -2, -3, -4):                           # chain32, chained + unpadded rows, chained, reduce-per-row
-        monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest, idx=idx: cands[max(idx, -len(cands))]())
+        monkeypatch.setattr(C3, "_route", lambda kind, width, variants, idx=idx: variants[max(idx, -len(variants))])
+        assert C3._route("fwd", 16, C3._fwd_variants(x, w)) == C3._HIP_VARIANTS[idx]      # no cube kernel at 48 -> 48: the row kernels
         y = C3._ConvSame.apply(x, w, bias)
         got = torch.autograd.grad(y, (x, w, bias), dy)
         for a, b in zip((y,) + got, (y_want,) + want):
@@ -1067,9 +1067,8 @@ def test_segmamba_bf16_forward_with_library_convolutions_on_emulated_kernels(emu
     from segmamba_amd import conv3d as C3
     monkeypatch.setattr(L, "_lib", emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setenv("SEGM_CONV_FWD_UNTIMED", "1")
     routed = []
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: (routed.append(len(cands)), cands[-1]())[1])
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: (routed.append(len(variants)), variants[-1])[1])
     from model_segmamba.segmamba import SegMamba
     from tests.golden.make_golden import named_fill
     f = H.load_golden("segmamba_tiny.npz")
@@ -1351,11 +1350,11 @@ def test_pointwise_weight_gradient_takes_the_library_gemm(emu, monkeypatch):
 def test_concatenated_input_convolution_is_one_node_with_in_place_parts(emu, monkeypatch):
     """conv3d_same_cat((a, b), w) - the decoder's conv1 on cat(upsampled, skip) - as ONE autograd node: the second part is
     added in place by the library kernel (every variant), gradients of both parts and of the whole weight, against autograd of
-    conv3d on the materialised concatenation in fp32; and the route with an ordinary add (variant not tuned yet) gives the same"""
+    conv3d on the materialised concatenation in fp32; and the route with an ordinary add (the second part on the vendor route) gives the same"""
     from segmamba_amd import lib as L, conv3d as C3
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])
     monkeypatch.setattr(C3, "_CAT_FUSED", True)
     g = torch.Generator().manual_seed(8)
     a = torch.randn(1, 48, 2, 3, 64, generator=g).bfloat16().requires_grad_()
@@ -1368,10 +1367,20 @@ def test_concatenated_input_convolution_is_one_node_with_in_place_parts(emu, mon
     ref.backward(dy.float())
     outs = []
     for variant in (None,) + C3._HIP_VARIANTS:
-        monkeypatch.setattr(C3, "_tuned_variant", lambda key, cands, variants, *rest, v=variant: v)
+        fwd_routes = []
+
+        def route(kind, width, variants, variant=variant, fwd_routes=fwd_routes):
+            """the first part and the gradients: the last variant; the added part: `variant`"""
+            if kind != "fwd":
+                return variants[-1]
+            assert variant in variants
+            fwd_routes.append(variant if fwd_routes else variants[-1])
+            return fwd_routes[-1]
+        monkeypatch.setattr(C3, "_route", route)
         for t in (a, b, w):
             t.grad = None
         y = C3.conv3d_same_cat((a, b), w)
+        assert fwd_routes == [C3._HIP_VARIANTS[-1], variant]
         assert type(y.grad_fn).__name__ == "_ConvSameCatBackward"
         y.backward(dy)
         assert (y.float() - ref).abs().max() <= 2e-2 * float(ref.abs().max()), variant
@@ -1425,8 +1434,7 @@ def test_decoder_block_with_fused_concatenation_emulated(emu, monkeypatch):
     from segmamba_amd import lib as L, unet_blocks as UB, conv3d as C3, linear as LN
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())
-    monkeypatch.setattr(C3, "_tuned_variant", lambda key, cands, variants, *rest: variants[-1])
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])
     monkeypatch.setattr(LN, "_PW_MIN", 64)
     torch.manual_seed(3)
     blk = UB.UnetResBlock(96, 48)
@@ -1467,9 +1475,7 @@ def test_res_front_node_matches_the_two_convolutions_emulated(emu, monkeypatch, 
     from segmamba_amd import lib as L, conv3d as C3, linear as LN
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())
-    monkeypatch.setattr(C3, "_tuned_variant", lambda key, cands, variants, *rest: variants[-1])
-    monkeypatch.setattr(C3, "_pick_was_hip", lambda *a, **k: True)
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])
     monkeypatch.setattr(C3, "_CAT_FUSED", True)
     monkeypatch.setattr(LN, "_PW_MIN", 64)
     g = torch.Generator().manual_seed(31 + parts)
@@ -1512,40 +1518,50 @@ def test_res_front_node_matches_the_two_convolutions_emulated(emu, monkeypatch, 
 
 
 def test_every_routing_candidate_of_the_conv_dispatcher_runs_and_agrees(emu, monkeypatch):
-    """conv3d.py's tuner runs EVERY candidate of a key once (timing) before it picks: here each candidate of the forward, the data
-    gradient and the weight gradient of a 96 -> 48 layer is executed (vendor routes on the CPU, library routes on the emulator) and
-    compared with the first one - what the GPU's first step does, minus the clock"""
+    """Every variant conv3d.py lists for a call computes the same convolution: each variant of the forward, the data gradient and
+    the weight gradient of a 96 -> 48 layer is forced in turn through `_route` (the vendor route on the CPU, library routes on the
+    emulator) and compared with the first one; then a layer the cube kernels take"""
     from segmamba_amd import lib as L, conv3d as C3
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    seen = {}
+    real_route = C3._route
 
-    def run_all(key, cands, *rest):
-        outs = [c() for c in cands]
-        seen[key[0]] = len(cands)
-        for o in outs[1:]:
-            assert o.shape == outs[0].shape
-            assert (o.float() - outs[0].float()).abs().max() <= 3e-2 * max(1.0, float(outs[0].float().abs().max())), key[0]
-        return outs[-1]
+    def every_variant(x, w, b, dy):
+        """-> (the variant lists of the three calls, the statistics of the unforced forward)"""
+        lists = {}
 
-    monkeypatch.setattr(C3, "_pick", run_all)
+        def run(route):
+            monkeypatch.setattr(C3, "_route", route)
+            for t in (x, w, b):
+                if t is not None:
+                    t.grad = None
+            y, st = C3.conv3d_same(x, w, b, want_stats=True)
+            y.backward(dy)
+            assert w.grad.dtype == torch.float32 and x.grad.dtype == torch.bfloat16 and (b is None or b.grad.dtype == torch.float32)
+            return {"fwd": y.detach(), "dgrad": x.grad, "wgrad": w.grad}, st
+
+        first, st = run(lambda kind, width, variants: (lists.__setitem__(kind, variants), real_route(kind, width, variants))[1])
+        for kind in ("fwd", "dgrad", "wgrad"):
+            assert lists[kind][0] is None
+            for v in lists[kind][1:]:
+                o = run(lambda k, width, variants, kind=kind, v=v: v if k == kind else variants[0])[0][kind]
+                assert o.shape == first[kind].shape
+                assert (o.float() - first[kind].float()).abs().max() <= 3e-2 * max(1.0, float(first[kind].float().abs().max())), (kind, v)
+        return lists, st
+
     g = torch.Generator().manual_seed(21)
     x = torch.randn(1, 96, 2, 4, 16, generator=g).bfloat16().requires_grad_()
     w = (0.05 * torch.randn(48, 96, 3, 3, 3, generator=g)).requires_grad_()                 # fp32 master
     b = torch.randn(48, generator=g).requires_grad_()
-    y = C3.conv3d_same(x, w, b)
-    y.backward(torch.randn(y.shape, generator=g).bfloat16())
-    assert seen == {"fwd": 6, "dgrad": 7, "wgrad": 3}, seen       # vendor, blocked, four library variants (+ dgrad-as-forward)
-    assert w.grad.dtype == torch.float32 and b.grad.dtype == torch.float32 and x.grad.dtype == torch.bfloat16
-    # a layer the cube kernels take (96 -> 192 channels on an 8^3 volume): one more candidate each, the same results
-    seen.clear()
+    lists, _ = every_variant(x, w, b, torch.randn(1, 48, 2, 4, 16, generator=g).bfloat16())
+    assert lists["fwd"] == lists["dgrad"] == [None] + list(C3._HIP_VARIANTS), lists      # vendor + the four row kernels
+    assert lists["wgrad"] == [None, "mfma"], lists
+    # a layer the cube kernels take (96 -> 192 channels on an 8^3 volume): one more variant each, the same results
     x2 = torch.randn(1, 96, 8, 8, 8, generator=g).bfloat16().requires_grad_()
     w2 = (0.05 * torch.randn(192, 96, 3, 3, 3, generator=g)).requires_grad_()
-    y2, st = C3.conv3d_same(x2, w2, None, want_stats=True)
-    y2.backward(torch.randn(y2.shape, generator=g).bfloat16())
-    assert seen["fwd"] >= 2 and seen["dgrad"] >= 3 and seen["wgrad"] >= 2, seen
-    assert st is None                    # (without a GPU the dispatcher's own pick is the vendor route: it hands no statistics on)
-    assert w2.grad.dtype == torch.float32 and x2.grad.dtype == torch.bfloat16
+    lists, st = every_variant(x2, w2, None, torch.randn(1, 192, 8, 8, 8, generator=g).bfloat16())
+    assert lists["fwd"] == lists["dgrad"] == [None] + list(C3._HIP_VARIANTS) + ["cube"] and lists["wgrad"] == [None, "mfma", "cube"], lists
+    assert st is None                    # (without a GPU the unforced route is the vendor call: it hands no statistics on)
 
 
 @pytest.mark.parametrize("K,M,N,dtype,lda,ldb", [(5000, 96, 3, torch.bfloat16, 96, 40), (4096 + 77, 192, 6, torch.bfloat16, 192, 6),
@@ -1883,9 +1899,7 @@ def test_unet_res_block_with_statistics_from_the_convolutions_emulated(emu, monk
     from segmamba_amd import lib as L, unet_blocks as UB, conv3d as C3
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())     # the library's candidates: chain32 is the last variant
-    monkeypatch.setattr(C3, "_pick_was_hip", lambda *a: True)
-    monkeypatch.setattr(C3, "_tuned_variant", lambda key, cands, variants, width=0: variants[-1])
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])     # the library's candidates: chain32 is the last variant
     monkeypatch.setattr(C3, "_CAT_FUSED", cat_fused)
     torch.manual_seed(3)
     blk = UB.UnetResBlock(96, 48).bfloat16()

@@ -56,9 +56,7 @@ def test_res_block_same_bits_with_and_without_the_tail_emulated(emu, monkeypatch
     from segmamba_amd import conv3d as C3
     monkeypatch.setattr(L, "get_lib", lambda: emu)
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())     # the library's candidates, as in test_emu_kernels.py
-    monkeypatch.setattr(C3, "_pick_was_hip", lambda *a: True)
-    monkeypatch.setattr(C3, "_tuned_variant", lambda key, cands, variants, width=0: variants[-1])
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])     # the library's candidates, as in test_emu_kernels.py
     T.check_block("cpu", monkeypatch, channels, shapes)
 
 

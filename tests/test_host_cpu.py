@@ -166,8 +166,8 @@ def test_patch_convs_match_torch():
 
 
 def test_conv_dispatcher_routings_are_the_same_convolution():
-    """conv3d.py: every candidate the autotuner may pick (channel-blocked forward, data gradient as a forward convolution
-    with flipped weights, blocked weight gradient, cat-free decoder convolution) equals torch's conv3d autograd."""
+    """conv3d.py: the vendor routes of the data and the weight gradient, the cat-free decoder convolution and the bias path equal
+    torch's conv3d autograd."""
     import torch.nn.functional as F
     from segmamba_amd import conv3d as C3
     g = torch.Generator().manual_seed(2)
@@ -177,12 +177,8 @@ def test_conv_dispatcher_routings_are_the_same_convolution():
     dy = torch.randn(ref.shape, generator=g, dtype=torch.float64)
     gx, gw = torch.autograd.grad(ref, (x, w), dy)
     xd, wd = x.detach(), w.detach()
-    assert torch.allclose(C3._fwd_blocked(xd, wd, 1), ref, atol=1e-10)
     assert torch.allclose(C3._dgrad_native(dy, wd, xd, 1), gx, atol=1e-10)
-    assert torch.allclose(C3._dgrad_as_fwd(dy, wd, xd, 1), gx, atol=1e-10)
-    assert torch.allclose(C3._dgrad_as_fwd_blocked(dy, wd, xd, 1), gx, atol=1e-10)
     assert torch.allclose(C3._wgrad_native(xd, dy, wd, 1), gw, atol=1e-10)
-    assert torch.allclose(C3._wgrad_blocked(xd, dy, wd, 1), gw, atol=1e-10)
     # cat-free decoder convolution == convolution of the concatenation (unetr_block.py:82-84), values and gradients
     a = torch.randn(1, 48, 4, 5, 6, generator=g, dtype=torch.float64, requires_grad=True)
     b = torch.randn(1, 48, 4, 5, 6, generator=g, dtype=torch.float64, requires_grad=True)
@@ -350,9 +346,9 @@ def test_argument_errors_of_the_newer_entry_points_without_gpu(built_lib):
 def test_conv_routing_is_a_table_not_a_timing_run():
     """which kernel a 3x3x3 layer takes must not depend on a per-process timing run (ranks could differ, results
     were not reproducible run to run, nothing of it can happen under graph capture).  Routing is a pure function of the shape
-    (conv3d._table_choice, from profiles/r02_bench_variants.log); the tuner is opt-in (SEGM_CONV_AUTOTUNE=1)."""
+    (conv3d._table_choice, from profiles/r02_bench_variants.log); the module has no timing run and no state one could fill."""
+    import inspect
     from segmamba_amd import conv3d
-    assert conv3d._TUNE is False
     lib = [(False, False, False), (True, False, False), (True, True, False), (False, False, True)]
     fwd = [None, None] + lib                                  # native, blocked, the four library variants
     for width, want in ((128, (True, True, False)), (64, (False, False, True)), (32, (False, False, True)), (16, (False, False, True))):     # 64^3: the 32-wide kernel since round 4
@@ -363,8 +359,59 @@ def test_conv_routing_is_a_table_not_a_timing_run():
     assert conv3d._table_choice("fwd", 64, [None, lib[0]]) == 1                  # only the plain library kernel applies
     assert conv3d._table_choice("wgrad", 128, [None, None, "mfma"]) == 2 and conv3d._table_choice("wgrad", 16, [None, "mfma"]) == 1
     assert conv3d._table_choice("wgrad", 8, [None, None, "mfma"]) == 0
-    # the same decision in every process: no state is consulted
-    assert not conv3d._cache
+    # the same decision in every process: there is no timing state to consult and nothing that could time a kernel
+    assert not any(hasattr(conv3d, name) for name in ("_TUNE", "_cache", "_time"))
+    source = inspect.getsource(conv3d)
+    assert "synchronize" not in source and "elapsed_time" not in source
+
+
+_ROUTE_NAMES = {None: "vendor", (False, False, False): "plain", (True, False, False): "chain", (True, True, False): "chain_pitch48",
+                (False, False, True): "chain32", "mfma": "mfma", "cube": "cube"}
+
+
+def test_conv_routes_equal_the_recorded_table(monkeypatch):
+    """Which kernel a 3x3x3 layer takes is what it was before the routing became one function: for every (width, Cin, Cout) of the
+    grid the forward / data-gradient / weight-gradient routes equal tests/conv_routes_recorded.json, recorded from the dispatcher
+    that still built closures per call ("W:Cin>Cout" -> "fwd/dgrad/wgrad").  Sections: bf16 over the whole grid (channels capped per
+    width so that the untouched torch.empty volumes stay below ~0.5 GB); fp16; fp32 (vendor everywhere); x with a padded channel
+    stride (ops_raw.volume_empty's 192 elements, which the kernels take, and 4 elements, which they do not); the cube kernels
+    switched off.  No GPU: the applicability predicates read shapes, strides and dtypes only."""
+    import json
+    from segmamba_amd import conv3d as C3
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_routes_recorded.json")) as f:
+        recorded = json.load(f)
+
+    def volume(c, width, dtype, pad=0):
+        s = width ** 3
+        return torch.empty(1, c, s + pad, dtype=dtype)[:, :, :s].view(1, c, width, width, width)
+
+    def routes(width, cin, cout, dtype, pad):
+        x, dy, w = volume(cin, width, dtype, pad), volume(cout, width, dtype), torch.empty(cout, cin, 3, 3, 3, dtype=dtype)
+        lists = (("fwd", C3._fwd_variants(x, w)), ("dgrad", C3._fwd_variants(dy, w, flipped=True)), ("wgrad", C3._wgrad_variants(x, dy, w)))
+        for _, variants in lists:                        # the lists themselves: vendor first, no duplicates
+            assert variants[0] is None and len(set(variants)) == len(variants)
+        return "/".join(_ROUTE_NAMES[variants[C3._table_choice(kind, width, variants)]] for kind, variants in lists)
+
+    sections = {"bf16": (torch.bfloat16, 0, True), "fp16": (torch.float16, 0, True), "fp32": (torch.float32, 0, True),
+                "bf16_x_channel_pad_192": (torch.bfloat16, 192, True), "bf16_x_channel_pad_4": (torch.bfloat16, 4, True),
+                "bf16_cube_off": (torch.bfloat16, 0, False)}
+    assert set(recorded) == set(sections)
+    caps = {128: 96, 64: 192, 32: 384, 24: 96}
+    grid = {f"{width}:{cin}>{cout}" for width in (128, 64, 32, 24, 16, 8, 4) for cin in (4, 32, 48, 64, 96, 192, 384, 768)
+            for cout in (16, 48, 64, 96, 192, 384, 768) if max(cin, cout) <= caps.get(width, 768)}
+    assert set(recorded["bf16"]) == grid and set(recorded["bf16_cube_off"]) == grid
+    for name, (dtype, pad, cube) in sections.items():
+        monkeypatch.setattr(C3, "_CUBE", cube)
+        monkeypatch.setattr(C3, "_CUBE_WGRAD", cube)
+        for shape, want in recorded[name].items():
+            width, cin, cout = (int(t) for t in re.split("[:>]", shape))
+            assert routes(width, cin, cout, dtype, pad) == want, (name, shape)
+    spot = {"16:64>16": "vendor/plain/vendor", "16:96>16": "plain/chain32/vendor", "16:96>48": "chain32/chain32/mfma",
+            "16:96>96": "cube/cube/mfma", "16:384>384": "cube/cube/cube", "8:48>96": "vendor/vendor/vendor",
+            "8:32>96": "cube/vendor/vendor", "8:96>96": "cube/cube/vendor", "8:96>192": "cube/cube/cube"}
+    assert all(recorded["bf16"][k] == v for k, v in spot.items())
+    assert {v for k, v in recorded["bf16"].items() if k.startswith("4:")} == {"vendor/vendor/vendor"}
+    assert set(recorded["fp32"].values()) == {"vendor/vendor/vendor"}
 
 
 def test_conv_table_small_volumes_follow_the_logged_winners():

@@ -232,7 +232,7 @@ def test_derived_weight_packs_come_from_one_gather_and_change_nothing(monkeypatc
     from segmamba_amd.unet_blocks import UnetResBlock
     monkeypatch.setattr(L, "_lib", emu_util.emu_lib())
     monkeypatch.setattr(L, "on_device", lambda t: True)
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[-1]())      # the library's kernels wherever they apply
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[-1])      # the library's kernels wherever they apply
     from segmamba_amd import linear as LN
     monkeypatch.setattr(LN, "_ROWS_MIN", 1)                                      # ... also for 128 rows of tokens
     monkeypatch.setattr(LN, "_ROWS_HIP", True)

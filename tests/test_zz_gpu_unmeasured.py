@@ -42,13 +42,13 @@ def test_conv3d_k3_fwd_newer_chained_variants(hip, shape):
 def test_conv3d_same_autograd_with_newer_library_candidates(hip, monkeypatch, idx):
     """the dispatcher with its last (chained, 32-wide) / second-to-last (chained, unpadded rows) forward candidates forced in"""
     from segmamba_amd import conv3d as C3
-    monkeypatch.setenv("SEGM_CONV_FWD_UNTIMED", "1")
     g = torch.Generator(device=DEV).manual_seed(4)
     x = torch.randn(2, 48, 8, 16, 32, device=DEV, generator=g).bfloat16().requires_grad_()
     w = (0.05 * torch.randn(48, 48, 3, 3, 3, device=DEV, generator=g)).bfloat16().requires_grad_()
     bias = torch.randn(48, device=DEV, generator=g).bfloat16().requires_grad_()
     dy = torch.randn(2, 48, 8, 16, 32, device=DEV, generator=g).bfloat16()
-    monkeypatch.setattr(C3, "_pick", lambda key, cands, *rest: cands[idx if key[0] != "wgrad" else -1]())
+    monkeypatch.setattr(C3, "_route", lambda kind, width, variants: variants[max(idx, -len(variants)) if kind != "wgrad" else -1])
+    assert C3._route("fwd", 32, C3._fwd_variants(x, w)) == C3._route("dgrad", 32, C3._fwd_variants(dy, w, flipped=True)) == C3._HIP_VARIANTS[idx]
     y = C3.conv3d_same(x, w, bias)
     gx, gw, gb = torch.autograd.grad(y, (x, w, bias), dy)
     x2, w2, b2 = (t.detach().float().requires_grad_() for t in (x, w, bias))

@@ -2,17 +2,14 @@
 kernels running on the CPU emulation of HIP (tests/emu) - against the same step on the ATen CPU path, in fp32 and in bf16
 (the bf16 ATen run is the yardstick for what bf16 rounding alone does to the small gradients).
 
-    python tools/emu_full_model_check.py [conv candidate index, default -1 = the last library candidate] [--linear]
+    python tools/emu_full_model_check.py [conv variant index, default -1 = the last library variant] [--linear]
 
 `--linear` also switches the Mamba block's projections to segm_linear_rows (the SEGM_LINEAR_HIP route).
 
 Slow (about ten minutes on 8 cores): an integration check for the build container, where there is no GPU; not part of the
 pytest suite.  The Mamba operators have no CPU path, so all three runs use the (oracle-checked) emulated scan kernels."""
-import os
 import sys
 import time
-
-os.environ.setdefault("SEGM_CONV_FWD_UNTIMED", "1")     # every forward-convolution variant is a candidate here
 
 sys.path.insert(0, ".")
 import torch  # noqa: E402
@@ -39,7 +36,7 @@ def run(bf16: bool, library: bool):
         m = m.bfloat16()
     L.on_device = (lambda t: True) if library else (lambda t: False)
     LN._ROWS_HIP, LN._ROWS_MIN = (library and linear_route), 1
-    C3._pick = lambda key, cands: cands[max(idx, -len(cands)) if library else 0]()
+    C3._route = lambda kind, width, variants: variants[max(idx, -len(variants)) if library else 0]
     t0 = time.time()
     out = m(vol.bfloat16() if bf16 else vol)
     loss = train_ops.cross_entropy(out, lab) if library else torch.nn.functional.cross_entropy(out.float(), lab)

@@ -43,8 +43,7 @@ for cin, cout, S in LAYERS:
     img = ops_raw.conv3d_cube_weight_image(hip, w)
 
     def route():
-        key, cands, variants = C._fwd_candidates(x, w, None, 1)
-        return C._pick(key, cands, variants, x.shape[4])
+        return C._run_fwd(C._route("fwd", x.shape[4], C._fwd_variants(x, w)), x, w, 1)
 
     ms0 = t(route)
     out = "%3d -> %3d @%2d^3: present route %.3f ms (%4.0f TF/s) | cube" % (cin, cout, S, ms0, fl / ms0 * 1e-9)

@@ -46,8 +46,7 @@ for name, cin, cout, S, cnt in LAYERS:
     fl = 2.0 * B * S ** 3 * cin * cout * 27
 
     def fwd():
-        key, cands, variants = C._fwd_candidates(x, w, None, 1)
-        return C._pick(key, cands, variants, x.shape[4])
+        return C._run_fwd(C._route("fwd", x.shape[4], C._fwd_variants(x, w)), x, w, 1)
 
     ms = [t(fwd), t(lambda: C._dgrad(dy, w, x, 1)), t(lambda: C._wgrad(x, dy, w, 1, torch.float32))]
     say("%-32s %3d -> %3d @%3d^3 x%d:  %7.3f (%4.0f)   %7.3f (%4.0f)   %7.3f (%4.0f)" % (
