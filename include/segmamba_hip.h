@@ -1048,6 +1048,90 @@ typedef struct segm_planes_bbox_args {
 int segm_planes_bbox(const segm_planes_bbox_args* args);
 
 /* ------------------------------------------------------------------------------------------------
+ * Signed-distance and edge training targets (additive to ABI 10; csrc/sdm.hip).
+ * Replaces, of the reference's light_training/dataloading/dataset_sdm_edge.py: compute_sdf (:56-85: two
+ * scipy.ndimage.distance_transform_edt and skimage's find_boundaries(mode='inner') per region), get_edge_points / edge_3d (:33-54:
+ * `img - binary_erosion(img)`), and `seg_sdm = 1 - compute_sdf(seg) + seg_edge` of its `post` hook (:143-157).
+ * segm_sdm_masks makes the bit volumes, segm_edt_sq / segm_edt_sq_long transform their planes (unit spacing, int32, unchanged),
+ * segm_sdm_compose normalises, signs and adds.
+ * ------------------------------------------------------------------------------------------------ */
+enum segm_sdm_label_dtype { SEGM_SDM_LABEL_U8 = 0, SEGM_SDM_LABEL_I16 = 1, SEGM_SDM_LABEL_I64 = 2 };
+
+/* One stencil pass over n label volumes (n, depth, height, width), contiguous, read in their own dtype (no cast pass); a value
+ * outside [0, 255] belongs to no region.  `table` as above: bit r of table[l] = label l is in region r, r < n_regions.  Per volume
+ * four uint8 volumes of region bits, all written at every voxel:
+ *   inside    bit r set iff the voxel is in region r
+ *   outside   bit r set iff the voxel is not in region r, for r < n_regions (the bits above stay clear)
+ *   edge      bit r set iff the voxel is in the region and one of its six face neighbours is not, everything outside the volume
+ *             counting as not in the region: `img - binary_erosion(img, cross)` with border_value 0, segm_seg_regions' border rule
+ *   boundary  bit r set iff the voxel is in the region and one of its face neighbours INSIDE the volume is not: skimage's
+ *             find_boundaries(mode='inner') on a boolean image (dilation != erosion with reflecting borders, then the foreground).
+ *             A subset of `edge`; the two differ at region voxels on a face of the volume whose in-volume neighbours are all inside.
+ *   counts[v * 8 + r] = the voxels of volume v in region r (n x 8 int64, all OVERWRITTEN; unused regions 0)
+ * The four outputs overlap neither the labels nor one another.
+ * Rows along x go across the lanes, the neighbours in y and z come from the caches.  The counts go thread -> wave -> workgroup ->
+ * one 64-bit integer atomic per region that has a voxel in the workgroup: integers only, the order does not matter.
+ * SEGM_E_SHAPE: a side outside [1, SEGM_EDT_LONG_MAX_LINE], more than SEGM_METRICS_MAX_VOXELS voxels per volume, n outside
+ * [1, SEGM_METRICS_MAX_PLANES], n_regions outside [1, SEGM_METRICS_MAX_REGIONS], labels or counts not aligned to their element.
+ * SEGM_E_NULL: a NULL pointer.  SEGM_E_DTYPE: label_dtype not of segm_sdm_label_dtype.  Nothing is launched then. */
+typedef struct segm_sdm_masks_args {
+    int32_t depth, height, width;
+    int32_t n, n_regions, label_dtype;
+    const void* labels;            /* (n, depth, height, width) uint8, int16 or int64 */
+    const uint8_t* table;          /* 256 bytes, device memory */
+    uint8_t* inside;               /* (n, depth, height, width) each */
+    uint8_t* outside;
+    uint8_t* edge;
+    uint8_t* boundary;
+    int64_t* counts;               /* n x 8 values, device memory */
+    void* stream;
+} segm_sdm_masks_args;
+int segm_sdm_masks(const segm_sdm_masks_args* args);
+
+/* The targets of up to SEGM_METRICS_MAX_PLANES (volume, region) pairs from the bit volumes above and the int32 squared distance
+ * transforms of their planes.  Item i is region bit[i] of volume[i]; edt[pos_plane[i]] holds pos^2, the transform whose seeds are
+ * that bit of `outside`, edt[neg_plane[i]] holds neg^2, seeded by that bit of `inside`; c = counts[volume[i] * 8 + bit[i]] and
+ * live = 0 < c < voxels.  Two kernels:
+ *   maxima   Pmax^2 = max pos^2 and Nmax^2 = max neg^2 of every live item: thread -> wave -> workgroup, then one 32-bit integer
+ *            maximum per workgroup and item into the workspace, which the entry zeroes first.  pos^2 is read where the inside bit
+ *            is set and neg^2 where it is not (each is 0 elsewhere).
+ *   compose  per voxel, in fp64:  sdf = 0 if not live, else 0 exactly if the boundary bit is set, else
+ *            -sqrt(pos^2) / sqrt(Pmax^2) if the inside bit is set, else +sqrt(neg^2) / sqrt(Nmax^2);  sdm = 1 - sdf + edge.
+ *            This is compute_sdf's formula: both minima are 0 for a live region, one of the two distances is 0 at every voxel
+ *            (nothing cancels), and a live plane cannot divide by zero.  A plane that is not live never reads its transforms,
+ *            which hold the EDT's sentinel.
+ * Outputs, fp32, plane out_plane[i] of (n_out_planes, voxels) each, rounded from fp64 once: sdf, sdm, and edge as 0.0 / 1.0.  Each
+ * is nullable, at least one must be given; with sdf and sdm both NULL `edt` and `workspace` may be NULL and no maximum is taken.
+ * A thread takes 16-byte packets (four int32 of a plane, four bytes of a bit volume, one 16-byte store) where the item's planes
+ * and outputs are 16-byte aligned, single voxels otherwise and in the tail; both routes call one per-voxel function.
+ * Integer atomics only; no floating-point atomics: two calls are bit-equal.
+ * SEGM_E_SHAPE: voxels outside [1, SEGM_METRICS_MAX_VOXELS]; n_items outside [1, SEGM_METRICS_MAX_PLANES]; a volume, bit, plane or
+ * output plane index out of range; two items with one output plane; edt or an output not aligned to 4 bytes, counts to 8.
+ * SEGM_E_NULL: a required pointer is NULL, or no output is given.  SEGM_E_WORKSPACE, when sdf or sdm is given: workspace NULL, not
+ * aligned to 4 bytes or smaller than SEGM_SDM_COMPOSE_WORKSPACE_BYTES.  Nothing is launched then. */
+#define SEGM_SDM_COMPOSE_WORKSPACE_BYTES (2 * SEGM_METRICS_MAX_PLANES * 4)
+typedef struct segm_sdm_compose_args {
+    int64_t voxels;                /* depth * height * width <= SEGM_METRICS_MAX_VOXELS */
+    int32_t n_items, n_volumes, n_planes, n_out_planes;
+    int32_t volume[SEGM_METRICS_MAX_PLANES];
+    int32_t bit[SEGM_METRICS_MAX_PLANES];
+    int32_t pos_plane[SEGM_METRICS_MAX_PLANES];
+    int32_t neg_plane[SEGM_METRICS_MAX_PLANES];
+    int32_t out_plane[SEGM_METRICS_MAX_PLANES];
+    const int32_t* edt;            /* (n_planes, voxels) */
+    const uint8_t* inside;         /* (n_volumes, voxels) each */
+    const uint8_t* edge;
+    const uint8_t* boundary;
+    const int64_t* counts;         /* n_volumes x 8, as segm_sdm_masks wrote them */
+    float* sdf;                    /* (n_out_planes, voxels) each, nullable */
+    float* sdm;
+    float* edge_out;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_sdm_compose_args;
+int segm_sdm_compose(const segm_sdm_compose_args* args);
+
+/* ------------------------------------------------------------------------------------------------
  * Finishing a prediction on the device (additive to ABI 10; csrc/postprocess.hip, csrc/ccl_roots.hip).
  * Replaces, of the reference's light_training/prediction.py: predict_raw_probability (:33-62) + the argmax of 4_predict.py:81 +
  * predict_noncrop_probability (:64-108) by ONE launch, and large_connected_domain (:17-27: skimage.measure.label at connectivity 1,

@@ -19,17 +19,24 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from .metrics import BRATS_REGIONS
+
 
 class CaseDataset:
     """`<case>.npz` + `<case>.pkl`, or the `<case>.npy` / `<case>_seg.npy` that the reference's `unpack_dataset` leaves next to
     them (taken when present).  `paths` name the `.npz` files, as the reference's datalists do.  `__getitem__` returns the
     reference's dict - data (C, d, h, w) fp32, seg (1, d, h, w) (absent with `test`), properties - with the arrays on `device`.
     Uploaded cases are kept there while they fit in `cache_bytes`; the default is half of the device's free memory at construction
-    (a BraTS training set of 1251 cases of about 45 MB fits an MI355X), and every case when the device is the host."""
+    (a BraTS training set of 1251 cases of about 45 MB fits an MI355X), and every case when the device is the host.
+    `sdm_dir`: the folder of the `<case>_seg_sdm.npy` files of tools/make_sdm_targets.py (the reference's ./data/fullres/train_sdm);
+    the file's `[0]`, (3, d, h, w), is appended to the seg's channels, which become fp32, as the `__getitem__` of the reference's
+    dataset_sdm_edge.py does (:166-171)."""
 
-    def __init__(self, paths: Sequence[str], test: bool = False, device=None, cache_bytes: Optional[int] = None):
+    def __init__(self, paths: Sequence[str], test: bool = False, device=None, cache_bytes: Optional[int] = None,
+                 sdm_dir: Optional[str] = None):
         self.datalist = [str(p) for p in paths]
         self.test = test
+        self.sdm_dir = None if sdm_dir is None else str(sdm_dir)
         self.device = torch.device(device if device is not None else ("cuda" if torch.cuda.is_available() else "cpu"))
         if cache_bytes is None:
             cache_bytes = torch.cuda.mem_get_info(self.device)[0] // 2 if self.device.type == "cuda" else 1 << 62
@@ -53,6 +60,9 @@ class CaseDataset:
         image, seg = self.read_data(self.datalist[i])
         data = torch.from_numpy(np.array(image, dtype=np.float32)).to(self.device)            # a copy: the file may be mapped read-only
         seg = None if seg is None else torch.from_numpy(np.array(seg)).to(self.device)
+        if seg is not None and self.sdm_dir is not None:
+            sdm = np.load(os.path.join(self.sdm_dir, f"{self.data_cached[i]['name']}_seg_sdm.npy"), "r")[0]
+            seg = torch.cat([seg.float(), torch.from_numpy(np.array(sdm, dtype=np.float32)).to(self.device)])
         return data, seg
 
     def __getitem__(self, i):
@@ -80,14 +90,21 @@ class PatchLoader:
     `probabilistic_oversampling`; otherwise its box is uniform.  A case smaller than the patch is padded with zeros on both sides.
     All draws come from the global `np.random`, in the reference's order.  `seed` seeds the augmenter (`augment=True`: the batch of
     `next()` goes through `augment.DeviceAugmenter`; `augment="spline"`: through `augment.SplineAugmenter`; `augment="fused"`: through
-    `augment.FusedAugmenter`, the same chain with the intensity transforms and the mirror on the kernels of csrc/intensity.hip)."""
+    `augment.FusedAugmenter`, the same chain with the intensity transforms and the mirror on the kernels of csrc/intensity.hip).
+    `targets="sdm_edge"` enables `next_with_targets()`, which adds the edge masks and signed-distance maps of `regions`
+    (segmamba_amd/sdm.py), computed from the label as it leaves the augmenter."""
 
     def __init__(self, dataset, patch_size, batch_size: int = 2, oversample_foreground_percent: float = 0.33,
-                 probabilistic_oversampling: bool = False, device=None, augment: bool = False, seed: int = 42):
+                 probabilistic_oversampling: bool = False, device=None, augment: bool = False, seed: int = 42,
+                 targets: Optional[str] = None, regions=BRATS_REGIONS):
         self.dataset = dataset
         self.patch_size = [int(p) for p in patch_size]
         if len(self.patch_size) != 3 or min(self.patch_size) < 1:
             raise RuntimeError(f"PatchLoader: patch_size must be three positive ints, got {patch_size}")
+        if targets not in (None, "sdm_edge"):
+            raise RuntimeError(f"PatchLoader: targets must be None or 'sdm_edge', got {targets!r}")
+        self.targets = targets
+        self.regions = tuple(tuple(int(v) for v in r) for r in regions)
         self.batch_size = int(batch_size)
         self.keys = list(range(len(dataset)))
         self.oversample_foreground_percent = oversample_foreground_percent
@@ -173,3 +190,13 @@ class PatchLoader:
         if self.augmenter is not None:
             image, label = self.augmenter(image, label)
         return image, label
+
+    def next_with_targets(self):
+        """-> (image, label, edge, sdm): `next()`, then the edge masks and `1 - sdf + edge` of the label that `next()` returned, each
+        (B, R, *patch) fp32 (`sdm.sdm_edge_targets`): the targets of the augmented patch, not a warped copy of a whole-case file"""
+        if self.targets != "sdm_edge":
+            raise RuntimeError("PatchLoader.next_with_targets: construct the loader with targets='sdm_edge'")
+        from .sdm import sdm_edge_targets
+        image, label = self.next()
+        edge, sdm = sdm_edge_targets(label, self.regions)
+        return image, label, edge, sdm

@@ -332,6 +332,7 @@ EXPORTS = (
     "segm_seg_regions", "segm_seg_regions_workspace_bytes", "segm_edt_sq", "segm_border_distances", "segm_border_distances_workspace_bytes",
     "segm_border_stats", "segm_border_stats_workspace_bytes",
     "segm_edt_sq_long", "segm_edt_sq_long_workspace_bytes", "segm_planes_bbox",
+    "segm_sdm_masks", "segm_sdm_compose",
     "segm_resample_argmax", "segm_ccl_roots", "segm_ccl_roots_workspace_bytes", "segm_ccl_sizes", "segm_ccl_select",
     "segm_ccl_select_workspace_bytes",
     "segm_ccl_label_roots", "segm_ccl_label_roots_workspace_bytes", "segm_ccl_label_select", "segm_ccl_label_select_workspace_bytes",
@@ -415,6 +416,27 @@ class BorderStatsArgs(C.Structure):
                 ("edt_plane", C.c_int32 * METRICS_MAX_PLANES), ("item_group", C.c_int32 * METRICS_MAX_PLANES),
                 ("tolerance", C.c_float * METRICS_MAX_PLANES), ("rank", (C.c_int64 * 2) * METRICS_MAX_PLANES),
                 ("borders", C.c_void_p), ("edt", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+SDM_LABEL_U8, SDM_LABEL_I16, SDM_LABEL_I64 = 0, 1, 2                             # enum segm_sdm_label_dtype
+SDM_COMPOSE_WORKSPACE_BYTES = 2 * METRICS_MAX_PLANES * 4                       # SEGM_SDM_COMPOSE_WORKSPACE_BYTES
+
+
+class SdmMasksArgs(C.Structure):
+    _fields_ = [("depth", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("n", C.c_int32), ("n_regions", C.c_int32), ("label_dtype", C.c_int32),
+                ("labels", C.c_void_p), ("table", C.c_void_p), ("inside", C.c_void_p), ("outside", C.c_void_p), ("edge", C.c_void_p),
+                ("boundary", C.c_void_p), ("counts", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class SdmComposeArgs(C.Structure):
+    _fields_ = [("voxels", C.c_int64), ("n_items", C.c_int32), ("n_volumes", C.c_int32), ("n_planes", C.c_int32), ("n_out_planes", C.c_int32),
+                ("volume", C.c_int32 * METRICS_MAX_PLANES), ("bit", C.c_int32 * METRICS_MAX_PLANES),
+                ("pos_plane", C.c_int32 * METRICS_MAX_PLANES), ("neg_plane", C.c_int32 * METRICS_MAX_PLANES),
+                ("out_plane", C.c_int32 * METRICS_MAX_PLANES),
+                ("edt", C.c_void_p), ("inside", C.c_void_p), ("edge", C.c_void_p), ("boundary", C.c_void_p), ("counts", C.c_void_p),
+                ("sdf", C.c_void_p), ("sdm", C.c_void_p), ("edge_out", C.c_void_p),
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
 
 
@@ -750,6 +772,8 @@ class SegmLib:
         sig("segm_edt_sq_long", [C.POINTER(EdtSqLongArgs)], C.c_int)
         sig("segm_edt_sq_long_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_planes_bbox", [C.POINTER(PlanesBboxArgs)], C.c_int)
+        sig("segm_sdm_masks", [C.POINTER(SdmMasksArgs)], C.c_int)
+        sig("segm_sdm_compose", [C.POINTER(SdmComposeArgs)], C.c_int)
         sig("segm_resample_argmax", [C.POINTER(ResampleArgmaxArgs)], C.c_int)
         sig("segm_ccl_roots", [C.POINTER(CclRootsArgs)], C.c_int)
         sig("segm_ccl_roots_workspace_bytes", [C.c_int64], C.c_size_t)

@@ -1973,6 +1973,93 @@ def border_stats(lib: L.SegmLib, borders: torch.Tensor, edt: torch.Tensor, items
 
 
 # ---------------------------------------------------------------------------------------------------------
+# signed-distance and edge targets (csrc/sdm.hip): region bits with edges and inner boundaries, then sdf / sdm / edge planes
+# ---------------------------------------------------------------------------------------------------------
+_SDM_LABEL_DTYPES = {torch.uint8: L.SDM_LABEL_U8, torch.int16: L.SDM_LABEL_I16, torch.int64: L.SDM_LABEL_I64}
+
+
+def sdm_masks(lib: L.SegmLib, labels: torch.Tensor, table: torch.Tensor, n_regions: int):
+    """labels (n, D, H, W) uint8, int16 or int64, contiguous (a value outside 0 .. 255 is in no region); table (256,) uint8, bit r of
+    table[l] = label l belongs to region r < n_regions.  -> (bits, counts): bits (4, n, D, H, W) uint8 = the inside, outside, edge
+    and boundary bits of every volume (bit r = region r); counts (n, 8) int64 = the region sizes (still on the device)."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype not in _SDM_LABEL_DTYPES:
+        raise RuntimeError(f"sdm_masks: labels must be a uint8, int16 or int64 tensor, got {getattr(labels, 'dtype', type(labels))}")
+    if labels.dim() != 4 or not labels.is_contiguous():
+        raise RuntimeError(f"sdm_masks: labels must be contiguous (n, D, H, W), got shape {tuple(labels.shape)}")
+    n, D, H, W = labels.shape
+    if not 1 <= n <= L.METRICS_MAX_PLANES:
+        raise RuntimeError(f"sdm_masks: between 1 and {L.METRICS_MAX_PLANES} volumes per call, got {n}")
+    if min(D, H, W) < 1 or max(D, H, W) > L.EDT_LONG_MAX_LINE or D * H * W > L.METRICS_MAX_VOXELS:
+        raise RuntimeError(f"sdm_masks: sides in [1, {L.EDT_LONG_MAX_LINE}] and at most {L.METRICS_MAX_VOXELS} voxels per volume, got {(D, H, W)}")
+    n_regions = int(n_regions)
+    if not 1 <= n_regions <= L.METRICS_MAX_REGIONS:
+        raise RuntimeError(f"sdm_masks: between 1 and {L.METRICS_MAX_REGIONS} regions per call, got {n_regions}")
+    if not isinstance(table, torch.Tensor) or table.dtype != torch.uint8 or tuple(table.shape) != (256,) or not table.is_contiguous():
+        raise RuntimeError("sdm_masks: table must be a contiguous uint8 tensor of 256 entries")
+    if table.device != labels.device:
+        raise RuntimeError("sdm_masks: labels and table must be on one device")
+    bits = torch.empty(4, n, D, H, W, dtype=torch.uint8, device=labels.device)
+    counts = torch.empty(n, L.METRICS_MAX_REGIONS, dtype=torch.int64, device=labels.device)
+    a = L.SdmMasksArgs()
+    a.depth, a.height, a.width, a.n, a.n_regions, a.label_dtype = D, H, W, n, n_regions, _SDM_LABEL_DTYPES[labels.dtype]
+    a.labels, a.table = labels.data_ptr(), table.data_ptr()
+    a.inside, a.outside, a.edge, a.boundary = (bits[k].data_ptr() for k in range(4))
+    a.counts, a.stream = counts.data_ptr(), L.stream_handle(labels)
+    lib.check(lib.dll.segm_sdm_masks(a), "sdm_masks")
+    return bits, counts
+
+
+def sdm_compose(lib: L.SegmLib, bits: torch.Tensor, counts: torch.Tensor, edt: Optional[torch.Tensor], items, sdf: torch.Tensor = None,
+                sdm: torch.Tensor = None, edge: torch.Tensor = None) -> None:
+    """bits, counts as `sdm_masks` returns them; edt (P, D, H, W) int32 squared distances at unit spacing (None when only `edge` is
+    asked for); items: (volume, bit, pos plane, neg plane, output plane) - pos plane = the transform seeded by that bit of
+    bits[1] (outside), neg plane = by that bit of bits[0] (inside).  Writes plane `output plane` of the given outputs, each
+    (Q, D, H, W) fp32 contiguous: sdf, sdm = 1 - sdf + edge, edge as 0.0 / 1.0."""
+    if not isinstance(bits, torch.Tensor) or bits.dtype != torch.uint8 or bits.dim() != 5 or bits.shape[0] != 4 or not bits.is_contiguous():
+        raise RuntimeError("sdm_compose: bits must be the contiguous (4, n, D, H, W) uint8 tensor of sdm_masks")
+    n, shape = bits.shape[1], tuple(bits.shape[2:])
+    N = bits[0, 0].numel()
+    if N == 0 or N > L.METRICS_MAX_VOXELS:
+        raise RuntimeError(f"sdm_compose: between 1 and {L.METRICS_MAX_VOXELS} voxels per volume, got shape {shape}")
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int64 or tuple(counts.shape) != (n, L.METRICS_MAX_REGIONS) \
+            or not counts.is_contiguous() or counts.device != bits.device:
+        raise RuntimeError(f"sdm_compose: counts must be the contiguous ({n}, {L.METRICS_MAX_REGIONS}) int64 tensor of sdm_masks")
+    outs = [t for t in (sdf, sdm, edge) if t is not None]
+    if not outs:
+        raise RuntimeError("sdm_compose: at least one of sdf, sdm and edge is required")
+    for t in outs:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 4 or tuple(t.shape[1:]) != shape or not t.is_contiguous() \
+                or t.device != bits.device or t.shape[0] != outs[0].shape[0]:
+            raise RuntimeError(f"sdm_compose: outputs must be contiguous fp32 (Q, {', '.join(str(s) for s in shape)}) tensors of one Q on the bits' device")
+    dist = sdf is not None or sdm is not None
+    if dist:
+        if not isinstance(edt, torch.Tensor) or edt.dtype != torch.int32 or edt.dim() != 4 or tuple(edt.shape[1:]) != shape \
+                or not edt.is_contiguous() or edt.device != bits.device:
+            raise RuntimeError("sdm_compose: edt must be a contiguous (P, D, H, W) int32 tensor of the bits' volume shape and device")
+    items = [tuple(int(v) for v in it) for it in items]
+    if not 1 <= len(items) <= L.METRICS_MAX_PLANES or any(len(it) != 5 for it in items):
+        raise RuntimeError(f"sdm_compose: between 1 and {L.METRICS_MAX_PLANES} items (volume, bit, pos plane, neg plane, output plane)")
+    n_planes = edt.shape[0] if dist else 0
+    for v, b, pp, npl, o in items:
+        if not (0 <= v < n and 0 <= b < L.METRICS_MAX_REGIONS and 0 <= o < outs[0].shape[0]):
+            raise RuntimeError(f"sdm_compose: item (volume {v}, bit {b}, output plane {o}) out of range")
+        if dist and not (0 <= pp < n_planes and 0 <= npl < n_planes):
+            raise RuntimeError(f"sdm_compose: planes ({pp}, {npl}) outside the {n_planes} planes of edt")
+    if len({it[4] for it in items}) != len(items):
+        raise RuntimeError("sdm_compose: two items write one output plane")
+    ws = torch.empty(L.SDM_COMPOSE_WORKSPACE_BYTES // 4, dtype=torch.int32, device=bits.device) if dist else None     # the maxima
+    a = L.SdmComposeArgs()
+    a.voxels, a.n_items, a.n_volumes, a.n_planes, a.n_out_planes = N, len(items), n, n_planes, outs[0].shape[0]
+    for i, (v, b, pp, npl, o) in enumerate(items):
+        a.volume[i], a.bit[i], a.pos_plane[i], a.neg_plane[i], a.out_plane[i] = v, b, pp, npl, o
+    a.edt = edt.data_ptr() if dist else None
+    a.inside, a.edge, a.boundary, a.counts = bits[0].data_ptr(), bits[2].data_ptr(), bits[3].data_ptr(), counts.data_ptr()
+    a.sdf, a.sdm, a.edge_out = L.fptr(sdf), L.fptr(sdm), L.fptr(edge)
+    a.workspace, a.workspace_bytes, a.stream = L.fptr(ws), L.SDM_COMPOSE_WORKSPACE_BYTES if dist else 0, L.stream_handle(bits)
+    lib.check(lib.dll.segm_sdm_compose(a), "sdm_compose")
+
+
+# ---------------------------------------------------------------------------------------------------------
 # finishing a prediction (csrc/postprocess.hip, csrc/ccl_roots.hip): logits -> labels, connected components, sizes, selection
 # ---------------------------------------------------------------------------------------------------------
 def _same_volume(t, what: str, dtype, shape, device) -> None:
@@ -2925,7 +3012,7 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "instnorm_bwd", "instnorm_tail_bwd", "transpose_add", "layernorm_tokens_fwd", "layernorm_tokens_bwd", "sgd_clip_step", "cross_entropy",
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
-              "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "border_stats", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
+              "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "border_stats", "sdm_masks", "sdm_compose", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
               "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "spline_coefs", "affine_spline3", "affine_labels",
               "zoom_nearest", "gauss_blur", "intensity_stats", "intensity_apply", "window_gather", "window_count", "window_blend",
               "window_finish"):
