@@ -261,11 +261,11 @@ def _run_fwd(v, x, w, pad, bias=None, into=None, stats_box=None, flipped=False, 
 
 def _add_part(into, v, x, w, pad, stats_box=None, flipped=False, like=None):
     """into += the convolution `_run_fwd(v, x, w, ...)` computes (the next part of a concatenated input; a second gradient of the
-    same tensor): by the library kernel's accumulate mode where it has one for this shape (Cout % 48 == 0; a data gradient's target
-    with dense channels), by an ordinary add otherwise"""
+    same tensor): by the library kernel's accumulate mode where it has one for this shape (Cout % 48 == 0) and `into` has dense
+    channels (a vendor-route result or another consumer's gradient may not), by an ordinary add otherwise"""
     from . import ops_raw
     cout = w.shape[1] if flipped else w.shape[0]
-    if _is_lib(v) and cout % _BLOCK == 0 and (not flipped or ops_raw.channel_dense(into)):
+    if _is_lib(v) and cout % _BLOCK == 0 and ops_raw.channel_dense(into):
         return _run_fwd(v, x, w, pad, into=into, stats_box=stats_box, flipped=flipped)
     return into.add_(_run_fwd(v, x, w, pad, flipped=flipped, like=like))
 

@@ -522,14 +522,30 @@ def conv3d_cl_weight_image(lib: L.SegmLib, w: torch.Tensor, dtype=None) -> torch
     return flat[idx].view(14, 9, 64, 8).to(dtype or w.dtype).contiguous()
 
 
+def _check_out(name: str, out: torch.Tensor, x: torch.Tensor, shape) -> None:
+    """`out` of a kernel that takes it as a raw pointer + four strides: the shape the launch writes, x's dtype and device, unit
+    stride along the last dimension, 16-byte rows"""
+    if tuple(out.shape) != tuple(shape) or out.dtype != x.dtype or out.device != x.device or out.stride(4) != 1 or \
+            any(out.stride(i) % 8 or out.stride(i) <= 0 for i in range(4)) or out.data_ptr() % 16:
+        raise RuntimeError(f"{name}: `out` must be a {tuple(shape)} tensor of x's dtype on x's device, last dimension contiguous, 16-byte rows")
+
+
+def _check_w_image(name: str, w_image: torch.Tensor, x: torch.Tensor, numel: int) -> None:
+    if w_image.dtype != x.dtype or w_image.device != x.device or not w_image.is_contiguous() or w_image.numel() != numel:
+        raise RuntimeError(f"{name}: `w_image` must be a contiguous image of {numel} elements of x's dtype on x's device")
+
+
 def conv3d_k3_fwd_cl(lib: L.SegmLib, x: torch.Tensor, w_image: torch.Tensor, bias=None, out=None, accumulate=False, waves8=False):
     """y (B, D, H, W, 48) = conv3d(x (B, D, H, W, 48) channel-last, 3x3x3, stride 1, pad 1); bf16 / fp16."""
     if x.dim() != 5 or x.shape[4] != 48 or x.stride(4) != 1 or x.dtype not in (torch.bfloat16, torch.float16):
         raise RuntimeError("conv3d_k3_fwd_cl: x must be a (B, D, H, W, 48) 16-bit tensor with contiguous channels")
     B, D, H, W, _ = x.shape
-    y = out if out is not None else torch.empty(B, D, H, W, 48, dtype=x.dtype, device=x.device)
     if accumulate and out is None:
         raise RuntimeError("conv3d_k3_fwd_cl: accumulate needs `out`")
+    _check_w_image("conv3d_k3_fwd_cl", w_image, x, 14 * 9 * 64 * 8)
+    if out is not None:
+        _check_out("conv3d_k3_fwd_cl", out, x, (B, D, H, W, 48))
+    y = out if out is not None else torch.empty(B, D, H, W, 48, dtype=x.dtype, device=x.device)
     a = L.Conv3dClArgs()
     a.batch, a.channels, a.depth, a.height, a.width = B, 48, D, H, W
     a.dtype = L.dtype_code(x)
@@ -602,8 +618,9 @@ def conv3d_cube_weight_image(lib: L.SegmLib, w: torch.Tensor, flipped: bool = Fa
 
 
 def cube_pack_descs(items, device) -> tuple:
-    """items: [(src_off, out_off, cout_w, cin_w, co_stride, flipped)] -> (int32 (n, 8) device tensor laid out as
-    segm_cube_pack_desc, total blocks) for conv3d_cube_pack_multi"""
+    """items: [(src_off, out_off, cout_w, cin_w, co_stride, flipped)] -> (int32 (n, 10) device tensor laid out as the 40-byte
+    segm_cube_pack_desc {src_off lo, src_off hi, out_off lo, out_off hi, cout_w, cin_w, co_stride, flipped, first_block, reserved},
+    total blocks) for conv3d_cube_pack_multi"""
     rows, first = [], 0
     for src_off, out_off, cout_w, cin_w, co_stride, flipped in items:
         rows.append([src_off & 0xffffffff, src_off >> 32, out_off & 0xffffffff, out_off >> 32, cout_w, cin_w, co_stride, int(bool(flipped)), first, 0])
@@ -631,7 +648,8 @@ def conv3d_cube_plan(lib: L.SegmLib, B, cin, cout, D, H, W, nt=0, splits=0):
 def conv3d_k3_cube_fwd(lib: L.SegmLib, x: torch.Tensor, w_image: torch.Tensor, cout: int, bias=None, out=None, accumulate=False,
                        nt=0, splits=0, want_stats=False):
     """y (B, cout, D, H, W) = conv3d(x (B, Cin, D, H, W), 3x3x3, stride 1, pad 1) through the cube kernel; bf16 / fp16.  The
-    fp32 partial sums live in a per-device scratch buffer that grows to the largest layer seen (stream-ordered reuse).
+    fp32 partial sums of a split contraction live in a workspace allocated per call (none with one split).  `out` and `w_image`
+    reach the kernel as raw pointers: both are checked here (RuntimeError).
     want_stats: -> (y, stats), stats = fp32 (B, cout, nparts, 4) partial {count, sum, sum of squares, -} of what the launch stored
     (per wave of the storing launch: 128 or 512 voxels), for instnorm_fwd(..., stats=stats)."""
     if not conv3d_cube_supported(x, cout):
@@ -639,6 +657,9 @@ def conv3d_k3_cube_fwd(lib: L.SegmLib, x: torch.Tensor, w_image: torch.Tensor, c
     B, cin, D, H, W = x.shape
     if accumulate and out is None:
         raise RuntimeError("conv3d_k3_cube_fwd: accumulate needs `out`")
+    _check_w_image("conv3d_k3_cube_fwd", w_image, x, cout * cin * 27)
+    if out is not None:
+        _check_out("conv3d_k3_cube_fwd", out, x, (B, cout, D, H, W))
     y = out if out is not None else torch.empty(B, cout, D, H, W, dtype=x.dtype, device=x.device)
     nt, splits, need = conv3d_cube_plan(lib, B, cin, cout, D, H, W, nt, splits)
     # the partial sums of this call (none with one split): a fresh tensor per call - the caching allocator hands the same block back
