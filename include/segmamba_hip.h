@@ -1605,7 +1605,9 @@ int segm_softmax_dice_bwd(const segm_softmax_dice_args* args);
  * Replaces the reference's resample_data_or_seg without a separate z axis (light_training/preprocessing/resampling/
  * default_resampling.py:126-217 as default_preprocessor.py:187-201 calls it): skimage's resize(order 3 or 1, mode='edge',
  * anti_aliasing=False, clip=True) for the data - for n-D input scipy.ndimage.zoom(mode='nearest', grid_mode=True) - and
- * batchgenerators' resize_segmentation(order 1) for the seg.  Non-finite input values are outside the contract.
+ * batchgenerators' resize_segmentation(order 1) for the seg.  Its separate-z branch (:154-207; every slice resized in its plane, the
+ * nearest slice along the coarse axis) is segm_zoom_slices / segm_zoom_labels_slices below, for order_z = 0; order_z > 0 is not
+ * covered.  Non-finite input values are outside the contract.
  * ------------------------------------------------------------------------------------------------ */
 #define SEGM_ZOOM_MAX_SIDE 2048
 
@@ -1649,6 +1651,51 @@ typedef struct segm_zoom_labels_args {
     void* stream;
 } segm_zoom_labels_args;
 int segm_zoom_labels(const segm_zoom_labels_args* args);
+
+/* The separate-z branch of resample_data_or_seg (default_resampling.py:154-207) with order_z = 0: every slice is resized in its own
+ * plane, and output slice k is the resized input slice source[k] - the nearest slice, which the caller computes as
+ * clip(floor((n_in / n_out) * (k + 0.5) - 0.5 + 0.5), 0, n_in - 1) in float64 (scipy's map_coordinates(order=0, mode='nearest')).
+ * data (channels, slices, height, width) fp32, the slice axis outermost: element strides for channel, slice and y, unit stride along
+ * x -> out (channels, out_slices, out_height, out_width) fp32, dense.  source: out_slices int32 on the device; the kernel clamps
+ * them to [0, slices), so no table reads outside the input.
+ *   order 3: the prefilter of segm_zoom along x and y only - fp64 coefficients (channels, slices, height + 4, width + 4), no pass and
+ *            no margin along the slice axis - and 16 taps per output voxel; order 1: four taps of the fp32 input.
+ * clip = 1 clamps every output slice to the minimum and maximum of ITS SOURCE SLICE (skimage's clip=True on a 2-D resize), not of
+ * the channel; then the result is rounded to fp32.  Where out_height == height and out_width == width the slices are copied as they
+ * are (the reference's factor-1 resize reproduces them only up to fp64 rounding).  Several outputs that share a source slice are
+ * each computed.  Fixed summation orders, no floating-point atomics: two calls are bit-equal.
+ * Limits (SEGM_E_SHAPE, nothing is launched): as for segm_zoom, the slice axis counting as a side.
+ * Workspace: 2 * channels * slices 32-bit keys rounded up to 256 bytes, and - for order 3 with a changed in-plane shape - the
+ * coefficients behind them. */
+typedef struct segm_zoom_slices_args {
+    int32_t channels, slices, height, width;
+    int32_t out_slices, out_height, out_width;
+    int32_t order, clip, reserved;
+    int64_t stride_c, stride_s, stride_y;
+    const float* data;
+    const int32_t* source;
+    float* out;
+    void* workspace;     size_t workspace_bytes;
+    void* stream;
+} segm_zoom_slices_args;
+size_t segm_zoom_slices_workspace_bytes(int32_t channels, int32_t slices, int32_t height, int32_t width, int32_t out_height,
+                                        int32_t out_width, int32_t order);
+int segm_zoom_slices(const segm_zoom_slices_args* args);
+
+/* The same branch for a seg: seg (slices, height, width) int16, contiguous -> out (out_slices, out_height, out_width) int16.  Per
+ * output voxel the bilinear weights of its 4 corners in slice source[k] (clamped as above) are summed in fp64 per distinct corner
+ * label; the largest label whose sum is >= 0.5 wins, 0 if there is none (resize_segmentation(slice, shape, 1)).  Label -1 takes part
+ * like any other.  counts as for segm_zoom_labels (optional, OVERWRITTEN).  Limits as for segm_zoom_slices. */
+typedef struct segm_zoom_labels_slices_args {
+    int32_t slices, height, width;
+    int32_t out_slices, out_height, out_width;
+    const int16_t* seg;
+    const int32_t* source;
+    int16_t* out;
+    int64_t* counts;
+    void* stream;
+} segm_zoom_labels_slices_args;
+int segm_zoom_labels_slices(const segm_zoom_labels_slices_args* args);
 
 
 /* ------------------------------------------------------------------------------------------------

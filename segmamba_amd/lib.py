@@ -343,6 +343,7 @@ EXPORTS = (
     "segm_region_loss_workspace_bytes", "segm_region_loss_fwd", "segm_region_loss_bwd",
     "segm_softmax_dice_workspace_bytes", "segm_softmax_dice_fwd", "segm_softmax_dice_bwd",
     "segm_zoom", "segm_zoom_workspace_bytes", "segm_zoom_labels",
+    "segm_zoom_slices", "segm_zoom_slices_workspace_bytes", "segm_zoom_labels_slices",
     "segm_spline_coefs", "segm_spline_coefs_workspace_bytes", "segm_affine_spline3", "segm_affine_labels", "segm_zoom_nearest",
     "segm_gauss_blur",
     "segm_intensity_workspace_bytes", "segm_intensity_stats", "segm_intensity_apply",
@@ -601,6 +602,21 @@ class ZoomLabelsArgs(C.Structure):
                 ("seg", C.c_void_p), ("out", C.c_void_p), ("counts", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class ZoomSlicesArgs(C.Structure):
+    _fields_ = [("channels", C.c_int32), ("slices", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("out_slices", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
+                ("order", C.c_int32), ("clip", C.c_int32), ("reserved", C.c_int32),
+                ("stride_c", C.c_int64), ("stride_s", C.c_int64), ("stride_y", C.c_int64),
+                ("data", C.c_void_p), ("source", C.c_void_p), ("out", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
+class ZoomLabelsSlicesArgs(C.Structure):
+    _fields_ = [("slices", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
+                ("out_slices", C.c_int32), ("out_height", C.c_int32), ("out_width", C.c_int32),
+                ("seg", C.c_void_p), ("source", C.c_void_p), ("out", C.c_void_p), ("counts", C.c_void_p), ("stream", C.c_void_p)]
+
+
 AUG_MAX_SAMPLES, AUG_MAX_VOLUMES, BLUR_MAX_RADIUS = 8, 64, 4                   # SEGM_AUG_MAX_SAMPLES / _VOLUMES, SEGM_BLUR_MAX_RADIUS
 
 
@@ -808,6 +824,9 @@ class SegmLib:
         sig("segm_zoom", [C.POINTER(ZoomArgs)], C.c_int)
         sig("segm_zoom_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_zoom_labels", [C.POINTER(ZoomLabelsArgs)], C.c_int)
+        sig("segm_zoom_slices", [C.POINTER(ZoomSlicesArgs)], C.c_int)
+        sig("segm_zoom_slices_workspace_bytes", [C.c_int32] * 7, C.c_size_t)
+        sig("segm_zoom_labels_slices", [C.POINTER(ZoomLabelsSlicesArgs)], C.c_int)
         sig("segm_spline_coefs", [C.POINTER(SplineCoefsArgs)], C.c_int)
         sig("segm_spline_coefs_workspace_bytes", [C.c_int32] * 5, C.c_size_t)
         sig("segm_affine_spline3", [C.POINTER(AffineSpline3Args)], C.c_int)

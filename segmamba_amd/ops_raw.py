@@ -2568,6 +2568,61 @@ def zoom_labels(lib: L.SegmLib, seg: torch.Tensor, new_shape, want_counts: bool 
     return out, counts
 
 
+def _zoom_source(source, out_slices: int, device, what: str) -> torch.Tensor:
+    """the slice table of the separate-z entries: `out_slices` integers -> int32 on the device, contiguous"""
+    t = source if isinstance(source, torch.Tensor) else torch.as_tensor(np.asarray(source))
+    if t.dim() != 1 or t.numel() != out_slices or t.dtype.is_floating_point or t.dtype == torch.bool:
+        raise RuntimeError(f"{what}: source holds one integer per output slice ({out_slices}), got {tuple(t.shape)} {t.dtype}")
+    return t.to(device=device, dtype=torch.int32).contiguous()
+
+
+def zoom_slices(lib: L.SegmLib, data: torch.Tensor, new_shape, source, order: int = 3, clip: bool = True) -> torch.Tensor:
+    """data (C, S, H, W) fp32 with a unit stride along x, C <= 8 -> (C,) + new_shape fp32: output slice k is input slice source[k]
+    (int32 on the device, or host integers; clamped to [0, S) by the kernel) resized in its plane as `zoom` resizes a volume - order 3
+    or 1 - and with `clip` clamped to the range of that slice alone.  The separate-z branch of the reference's `resample_data_or_seg`
+    with order_z = 0.  An unchanged in-plane shape copies the slices.  Two calls are bit-equal."""
+    C_, S, H, W, sc, ss, sy = _prep_data(data, "zoom_slices")
+    _zoom_shape((S, H, W), "zoom_slices: data")
+    new_shape = _zoom_shape(new_shape, "zoom_slices")
+    if order not in (1, 3):
+        raise RuntimeError(f"zoom_slices: order 1 or 3, got {order}")
+    src = _zoom_source(source, new_shape[0], data.device, "zoom_slices")
+    nbytes = lib.dll.segm_zoom_slices_workspace_bytes(C_, S, H, W, new_shape[1], new_shape[2], order)
+    if nbytes == 0:
+        raise RuntimeError(f"zoom_slices: no workspace size for {tuple(data.shape)} -> {new_shape}, order {order}")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=data.device)
+    out = torch.empty((C_,) + new_shape, dtype=torch.float32, device=data.device)
+    a = L.ZoomSlicesArgs()
+    a.channels, a.slices, a.height, a.width = C_, S, H, W
+    a.out_slices, a.out_height, a.out_width = new_shape
+    a.order, a.clip = order, 1 if clip else 0
+    a.stride_c, a.stride_s, a.stride_y = sc, ss, sy
+    a.data, a.source, a.out, a.workspace, a.workspace_bytes = data.data_ptr(), src.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes
+    a.stream = L.stream_handle(data)
+    lib.check(lib.dll.segm_zoom_slices(a), "zoom_slices")
+    return out
+
+
+def zoom_labels_slices(lib: L.SegmLib, seg: torch.Tensor, new_shape, source, want_counts: bool = True):
+    """seg (S, H, W) int16, contiguous -> (new_shape int16, counts int64 (260,) on the device or None): output slice k is
+    `resize_segmentation(seg[source[k]], new_shape[1:], 1)` - the largest label whose bilinear weight is >= 0.5, else 0 - and the label
+    counts of the result in `crop_normalize`'s layout."""
+    if not isinstance(seg, torch.Tensor) or seg.dim() != 3:
+        raise RuntimeError(f"zoom_labels_slices: a (S, H, W) seg is required, got {getattr(seg, 'shape', type(seg))}")
+    _same_volume(seg, "zoom_labels_slices: seg", torch.int16, tuple(seg.shape), seg.device)
+    S, H, W = _zoom_shape(seg.shape, "zoom_labels_slices: seg")
+    new_shape = _zoom_shape(new_shape, "zoom_labels_slices")
+    src = _zoom_source(source, new_shape[0], seg.device, "zoom_labels_slices")
+    out = torch.empty(new_shape, dtype=torch.int16, device=seg.device)
+    counts = torch.empty(L.PREP_COUNT_BINS, dtype=torch.int64, device=seg.device) if want_counts else None
+    a = L.ZoomLabelsSlicesArgs()
+    a.slices, a.height, a.width = S, H, W
+    a.out_slices, a.out_height, a.out_width = new_shape
+    a.seg, a.source, a.out, a.counts, a.stream = seg.data_ptr(), src.data_ptr(), out.data_ptr(), L.fptr(counts), L.stream_handle(seg)
+    lib.check(lib.dll.segm_zoom_labels_slices(a), "zoom_labels_slices")
+    return out, counts
+
+
 # ---------------------------------------------------------------------------------------------------------
 # augmentation at the reference's interpolation orders (csrc/augment.hip): spline coefficients, the affine warp of data and
 # labels, order-0 zoom, gaussian blur.  Matrices, sigmas and flags are host values and travel in the argument structs.
@@ -3034,7 +3089,7 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "conv1d_update", "state_update", "linear_rows", "skinny_tn", "pointwise_cf", "stem_conv_fwd", "stem_conv_wgrad", "wgrad_gemm",
               "scan_fwd_multi", "scan_bwd_multi", "conv1d_fwd_multi", "conv1d_bwd_multi", "channel_sum", "depth_to_space2",
               "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "border_stats", "sdm_masks", "sdm_compose", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
-              "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "spline_coefs", "affine_spline3", "affine_labels",
+              "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "zoom_slices", "zoom_labels_slices", "spline_coefs", "affine_spline3", "affine_labels",
               "zoom_nearest", "gauss_blur", "intensity_stats", "intensity_apply", "window_gather", "window_count", "window_blend",
               "window_finish"):
     globals()[_name] = _device_guard(globals()[_name])

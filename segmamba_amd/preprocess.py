@@ -53,6 +53,7 @@ from . import lib as L
 from . import ops_raw
 from .metrics import _to_device
 from .postprocess import _fill
+from . import resample as RS
 from .resample import compute_new_shape            # noqa: F401  (resampling/default_resampling.py:23-30)
 
 NUM_SAMPLES = 10000                   # _sample_foreground_locations (default_preprocessor.py:456-457)
@@ -284,13 +285,17 @@ def sample_foreground_locations(seg, classes_or_regions, seed: int = 1234, count
 
 
 def preprocess_case(data, seg, properties: dict, out_spacing=(1, 1, 1), all_labels=(1, 2, 3), use_mask_for_norm: bool = False,
-                    resample: bool = False, normalization: str = "zscore", foreground_intensity_properties_per_channel=None):
+                    resample: bool = False, normalization: str = "zscore", foreground_intensity_properties_per_channel=None,
+                    force_separate_z=False):
     """`run_case_npy` (default_preprocessor.py:154-227).  data (C, D, H, W); seg (1, D, H, W) / (D, H, W) or None; properties with
     `spacing` (SimpleITK's (x, y, z)).  -> (data (C, d, h, w) fp32, seg (1, d, h, w) int8 / int16) on the device; `properties` gains
     original_spacing_trans, target_spacing_trans, shape_before_cropping, bbox_used_for_cropping, shape_after_cropping_before_resample,
     shape_after_resample (plain ints, floats and lists) and class_locations (`sample_foreground_locations`).  With `resample` a crop
     whose `compute_new_shape` differs from its shape is resampled to it (data order 3, seg order 1: default_preprocessor.py:187-201);
     the class locations and the seg's dtype then come from the resampled seg.  Without it such a case raises NotImplementedError.
+    `force_separate_z` (False / None / True, with `resample`) is the reference's: True, or None on a spacing - the case's first, then
+    the target's - whose max / min exceeds 3 with one coarsest axis, resamples data and seg slice by slice across that axis and
+    takes the nearest slice along it (segmamba_amd/resample.py); the default False keeps the one 3-D zoom.
     `normalization="ct"` replaces the z-score by `CTNormalization` with the dataset's `foreground_intensity_properties_per_channel`
     (per channel mean, std, percentile_00_5, percentile_99_5; keys str(c) as in the reference, or ints): DefaultPreprocessor's
     `run_case_npy` (:154-227, `_normalize` :235-242)."""
@@ -322,8 +327,15 @@ def preprocess_case(data, seg, properties: dict, out_spacing=(1, 1, 1), all_labe
     if new_shape != crop_shape:
         # an invalid seg value was written as label 0 and would be lost in the zoom: the first counts flag it (on the device)
         invalid = counts[L.PREP_BIN_INVALID]
-        out = ops_raw.zoom(lib, out, new_shape, 3, True)
-        seg_out, counts = ops_raw.zoom_labels(lib, seg_out, new_shape)
+        do_separate_z, axis = RS.decide_separate_z(spacing_trans, target, force_separate_z)
+        if do_separate_z:
+            axis = RS._separate_axis(axis, 0)
+            out = RS._resample(out, new_shape, False, 3, separate_axis=axis)
+            seg_out, counts = RS._resample(seg_out[None], new_shape, True, 1, with_counts=True, separate_axis=axis)
+            seg_out = seg_out[0]
+        else:
+            out = ops_raw.zoom(lib, out, new_shape, 3, True)
+            seg_out, counts = ops_raw.zoom_labels(lib, seg_out, new_shape)
         counts[L.PREP_BIN_INVALID] = invalid
     c, top = _check_counts(counts)
     properties["original_spacing_trans"] = spacing_trans
@@ -342,10 +354,10 @@ class CasePreprocessor:
     `<case>.npz` (data, seg) and `<case>.pkl` (properties) into `output_dir`, one case after the other."""
 
     def __init__(self, base_dir, image_dir, data_filenames: Sequence[str] = (), seg_filename: str = "", use_mask_for_norm: bool = False,
-                 resample: bool = False):
+                 resample: bool = False, force_separate_z=False):
         self.base_dir, self.image_dir = str(base_dir), str(image_dir)
         self.data_filenames, self.seg_filename = list(data_filenames), seg_filename
-        self.use_mask_for_norm, self.resample = use_mask_for_norm, resample
+        self.use_mask_for_norm, self.resample, self.force_separate_z = use_mask_for_norm, resample, force_separate_z
         self.out_spacing, self.all_labels, self.output_dir = (1, 1, 1), (1, 2, 3), None
 
     def get_iterable_list(self):
@@ -370,7 +382,8 @@ class CasePreprocessor:
 
     def run_case(self, case_name):
         data, seg, properties = self.read_data(case_name)
-        data, seg = preprocess_case(data, seg, properties, self.out_spacing, self.all_labels, self.use_mask_for_norm, self.resample)
+        data, seg = preprocess_case(data, seg, properties, self.out_spacing, self.all_labels, self.use_mask_for_norm, self.resample,
+                                    force_separate_z=self.force_separate_z)
         return data, seg, properties
 
     def run_case_save(self, case_name):
@@ -394,10 +407,10 @@ class CTCasePreprocessor:
     label under the same name in `base_dir/label_dir`; single channel.  `run_plan` is the dataset fingerprint, `run` writes the
     reference's `<case>.npz` / `<case>.pkl` with the CT normalisation, one case after the other."""
 
-    def __init__(self, base_dir, image_dir, label_dir=None, data_type: str = "CT", resample: bool = True):
+    def __init__(self, base_dir, image_dir, label_dir=None, data_type: str = "CT", resample: bool = True, force_separate_z=False):
         self.base_dir, self.image_dir = str(base_dir), str(image_dir)
         self.label_dir = None if label_dir is None else str(label_dir)
-        self.data_type, self.resample = data_type, resample
+        self.data_type, self.resample, self.force_separate_z = data_type, resample, force_separate_z
         self.out_spacing, self.all_labels, self.output_dir = (1, 1, 1), (1, 2, 3), None
         self.foreground_intensity_properties_per_channel = None
 
@@ -421,7 +434,8 @@ class CTCasePreprocessor:
     def run_case(self, case_name):
         data, seg, properties = self.read_data(case_name)
         data, seg = preprocess_case(data, seg, properties, self.out_spacing, self.all_labels, False, self.resample, normalization="ct",
-                                    foreground_intensity_properties_per_channel=self.foreground_intensity_properties_per_channel)
+                                    foreground_intensity_properties_per_channel=self.foreground_intensity_properties_per_channel,
+                                    force_separate_z=self.force_separate_z)
         return data, seg, properties
 
     def run_case_save(self, case_name):

@@ -1,12 +1,14 @@
 """Prepare raw cases for training and prediction on the device: the reference's 2_preprocessing_mri.py.
 
     python tools/preprocess_cases.py --raw DIR --out DIR [--data-files t1.nii.gz t1ce.nii.gz ...] [--seg-file seg.nii.gz] [--mask-norm] [--resample]
+                                    [--separate-z {never,auto,always}]
     python tools/preprocess_cases.py --raw DIR --out DIR --ct --plan FILE [--label-dir NAME] [--labels 1 2] [--spacing z y x]
 
 `--raw` holds one directory per case, each with one NIfTI file per modality and, for training data, the segmentation.  Every case
 becomes `<case>.npz` (data, seg) and `<case>.pkl` (properties) in `--out`: what `segmamba_amd.dataloading.CaseDataset` and the
 reference's `MedicalDataset` read.  `--seg-file ""` prepares unlabelled cases.  `--resample` resamples cases whose spacing is not
-`--spacing` (without it such a case is an error).  See segmamba_amd/preprocess.py for the stated limits.
+`--spacing` (without it such a case is an error); `--separate-z` is the reference's `force_separate_z` for that step (never = False,
+the default: one 3-D zoom; auto = None: slice by slice across the one coarse axis of an anisotropic spacing; always = True).  See segmamba_amd/preprocess.py for the stated limits.
 
 `--ct` prepares CT cases the way of the reference's DefaultPreprocessor: `--raw` holds one NIfTI file per case, `--label-dir` names the
 directory beside it with the segmentations under the same file names (none: unlabelled cases), `--plan` is the file
@@ -36,11 +38,14 @@ def main():
     ap.add_argument("--labels", nargs="+", type=int, default=[1, 2, 3])
     ap.add_argument("--mask-norm", action="store_true", help="z-score over seg >= 0 only (use_mask_for_norm)")
     ap.add_argument("--resample", action="store_true", help="resample to --spacing (data order 3, seg order 1)")
+    ap.add_argument("--separate-z", choices=["never", "auto", "always"], default="never",
+                    help="resample across one coarse axis slice by slice, nearest slice along it (force_separate_z False / None / True)")
     ap.add_argument("--ct", action="store_true", help="CT cases: one file per case, CT normalisation from --plan, resampled")
     ap.add_argument("--plan", default=None, help="with --ct: the JSON tools/plan_cases.py wrote")
     ap.add_argument("--label-dir", default=None, help="with --ct: the directory beside --raw that holds the segmentations")
     args = ap.parse_args()
     raw = os.path.abspath(args.raw)
+    force_separate_z = {"never": False, "auto": None, "always": True}[args.separate_z]
     if args.ct:
         if args.plan is None:
             ap.error("--ct needs --plan FILE (tools/plan_cases.py)")
@@ -48,7 +53,7 @@ def main():
         with open(args.plan) as f:
             plan = json.load(f)
         spacing = args.spacing if args.spacing is not None else plan["fullres spacing"][::-1]
-        pre = CTCasePreprocessor(os.path.dirname(raw), os.path.basename(raw), args.label_dir)
+        pre = CTCasePreprocessor(os.path.dirname(raw), os.path.basename(raw), args.label_dir, force_separate_z=force_separate_z)
         t0 = time.perf_counter()
         written = pre.run([int(s) if s == int(s) else s for s in spacing], args.out, list(args.labels),
                           plan["intensity_statistics_per_channel"])
@@ -59,7 +64,7 @@ def main():
     if args.spacing is None:
         args.spacing = [1.0, 1.0, 1.0]
     pre = CasePreprocessor(os.path.dirname(raw), os.path.basename(raw), args.data_files, args.seg_file, use_mask_for_norm=args.mask_norm,
-                           resample=args.resample)
+                           resample=args.resample, force_separate_z=force_separate_z)
     t0 = time.perf_counter()
     spacing = [int(s) if s == int(s) else s for s in args.spacing]
     written = pre.run(spacing, args.out, list(args.labels))
