@@ -1930,6 +1930,71 @@ int segm_window_blend(const segm_stitch_args* args);
 int segm_window_finish(const segm_stitch_args* args);
 
 
+/* ------------------------------------------------------------------------------------------------
+ * Fused residual add + LayerNorm / RMSNorm over the last dimension, forward and backward (additive to ABI 10;
+ * csrc/add_norm.hip).  Replaces the Triton kernels behind mamba_ssm/ops/triton/layernorm.py - _layer_norm_fwd
+ * (layernorm.py:123-177) and _layer_norm_bwd (layernorm.py:293-377) - the native code of `layer_norm_fn`, `rms_norm_fn`,
+ * `RMSNorm` and of `Block` with fused_add_norm (mamba_simple.py:445-501).
+ * Operands: `rows` = M rows of `cols` = N elements, unit stride along a row, one row stride (in elements, >= N) per tensor.
+ * x, y, dy, dx have `dtype`; residual, residual_out, dresidual, dresidual_in have `res_dtype`, which is `dtype` or SEGM_F32;
+ * weight, bias, dweight, dbias are fp32 of N elements; mean, rstd fp32 of M elements.  `rms` != 0 selects the RMS form, which
+ * has no mean (the pointer is not used).
+ * Forward, all in fp32:
+ *   s = float(x) + float(residual)                (s = float(x) without a residual)
+ *   residual_out = round(s) to res_dtype          (when the pointer is given)
+ *   LayerNorm: mean = sum(s) / N, var = sum((s - mean)^2) / N        RMS: mean = 0, var = sum(s^2) / N
+ *   rstd = 1.0f / sqrtf(var + eps)                (IEEE square root and division)
+ *   y = round((s - mean) * rstd * weight + bias) to dtype
+ * The statistics come from the unrounded s, in two passes over the row, which stays in registers between them.
+ * Backward, from mean, rstd and the saved row x_saved = residual_out (when that pointer is given: res_dtype) or x (dtype):
+ *   xhat = (x_saved - mean) * rstd, wdy = weight * dy, c1 = sum(xhat * wdy) / N, c2 = sum(wdy) / N  (0 for RMS)
+ *   dx = (wdy - (xhat * c1 + c2)) * rstd + float(dresidual)          (the last term when the pointer is given)
+ *   dresidual_in = round(dx) to res_dtype (when the pointer is given); dx is rounded to dtype
+ *   dweight[j] = sum over rows of dy * xhat, dbias[j] = sum over rows of dy (dbias may be NULL)
+ * A workgroup walks a fixed share of the rows and leaves one fp32 partial row in the workspace; the partial rows are added in a
+ * fixed order.  No floating-point atomics: two calls are bit-equal.  How a row is laid over lanes depends on N and dtype only, so
+ * a row's y, residual_out, dx and dresidual_in do not depend on M or on the other rows.  A lane takes packets of 16 bytes of x
+ * (4 fp32, 8 fp16 / bf16): whole packets where N is a multiple of the packet, every row stride in use too and every pointer in
+ * use is 16-byte aligned; element by element otherwise.  Both routes keep the same elements in the same lanes and call the same
+ * per-element functions: they give the same bits.
+ * Refused with nothing launched: cols outside [1, SEGM_ADD_NORM_MAX_COLS], rows outside [1, 2^31), a row stride of a tensor in
+ * use below cols, a pointer not aligned to its element (SEGM_E_SHAPE); an unknown dtype, a res_dtype that is neither dtype nor
+ * SEGM_F32 (SEGM_E_DTYPE); a required pointer that is NULL (SEGM_E_NULL: forward x, y, weight, rstd, and mean unless rms;
+ * backward dy, dx, weight, rstd, dweight, x or residual_out, and mean unless rms); backward only, a workspace that is NULL or
+ * smaller than segm_add_norm_workspace_bytes (SEGM_E_WORKSPACE).  No host synchronisation, everything on `stream`.
+ * ------------------------------------------------------------------------------------------------ */
+#define SEGM_ADD_NORM_MAX_COLS 8192
+
+typedef struct segm_add_norm_args {
+    int64_t rows;
+    int32_t cols, dtype, res_dtype, rms;
+    float eps;
+    int32_t reserved;
+    const void* x;              int64_t x_stride;              /* forward; backward: x_saved when residual_out is NULL */
+    const void* residual;       int64_t residual_stride;       /* forward, optional */
+    void* y;                    int64_t y_stride;              /* forward */
+    void* residual_out;         int64_t residual_out_stride;   /* forward: optional, written; backward: optional, x_saved */
+    const float* weight;
+    const float* bias;                                         /* forward, optional */
+    float* mean;                                               /* forward: written; backward: read */
+    float* rstd;
+    const void* dy;             int64_t dy_stride;             /* backward */
+    const void* dresidual;      int64_t dresidual_stride;      /* backward, optional */
+    void* dx;                   int64_t dx_stride;             /* backward */
+    void* dresidual_in;         int64_t dresidual_in_stride;   /* backward, optional */
+    float* dweight;                                            /* backward */
+    float* dbias;                                              /* backward, optional */
+    void* workspace;                                           /* backward */
+    size_t workspace_bytes;
+    void* stream;
+} segm_add_norm_args;
+
+/* 0 for a shape out of range */
+size_t segm_add_norm_workspace_bytes(int64_t rows, int32_t cols);
+int segm_add_norm_fwd(const segm_add_norm_args* args);
+int segm_add_norm_bwd(const segm_add_norm_args* args);
+
+
 /* ------------------------------------------------------------------------------------------------ */
 int segm_abi_version(void);
 const char* segm_status_string(int status);

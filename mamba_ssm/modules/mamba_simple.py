@@ -1,2 +1,2 @@
-"""Drop-in for reference mamba/mamba_ssm/modules/mamba_simple.py (class `Mamba`)."""
-from segmamba_amd.mamba_simple import Mamba  # noqa: F401
+"""Drop-in for reference mamba/mamba_ssm/modules/mamba_simple.py (classes `Mamba` and `Block`)."""
+from segmamba_amd.mamba_simple import Block, Mamba  # noqa: F401

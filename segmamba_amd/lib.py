@@ -348,6 +348,7 @@ EXPORTS = (
     "segm_gauss_blur",
     "segm_intensity_workspace_bytes", "segm_intensity_stats", "segm_intensity_apply",
     "segm_window_gather", "segm_window_count", "segm_window_blend", "segm_window_finish",
+    "segm_add_norm_fwd", "segm_add_norm_bwd", "segm_add_norm_workspace_bytes",
     "segm_abi_version", "segm_status_string",
 )
 
@@ -694,6 +695,21 @@ class StitchArgs(C.Structure):
                 ("pred", C.c_void_p), ("acc", C.c_void_p), ("total", C.c_void_p), ("stream", C.c_void_p)]
 
 
+ADD_NORM_MAX_COLS = 8192                                                       # SEGM_ADD_NORM_MAX_COLS
+
+
+class AddNormArgs(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("cols", C.c_int32), ("dtype", C.c_int32), ("res_dtype", C.c_int32), ("rms", C.c_int32),
+                ("eps", C.c_float), ("reserved", C.c_int32),
+                ("x", C.c_void_p), ("x_stride", C.c_int64), ("residual", C.c_void_p), ("residual_stride", C.c_int64),
+                ("y", C.c_void_p), ("y_stride", C.c_int64), ("residual_out", C.c_void_p), ("residual_out_stride", C.c_int64),
+                ("weight", C.c_void_p), ("bias", C.c_void_p), ("mean", C.c_void_p), ("rstd", C.c_void_p),
+                ("dy", C.c_void_p), ("dy_stride", C.c_int64), ("dresidual", C.c_void_p), ("dresidual_stride", C.c_int64),
+                ("dx", C.c_void_p), ("dx_stride", C.c_int64), ("dresidual_in", C.c_void_p), ("dresidual_in_stride", C.c_int64),
+                ("dweight", C.c_void_p), ("dbias", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("stream", C.c_void_p)]
+
+
 def header_abi_version() -> int:
     """SEGM_ABI_VERSION as include/segmamba_hip.h declares it (what a freshly built library must report)"""
     import re
@@ -838,6 +854,9 @@ class SegmLib:
         sig("segm_intensity_apply", [C.POINTER(IntensityArgs)], C.c_int)
         for n in ("segm_window_gather", "segm_window_count", "segm_window_blend", "segm_window_finish"):
             sig(n, [C.POINTER(StitchArgs)], C.c_int)
+        sig("segm_add_norm_fwd", [C.POINTER(AddNormArgs)], C.c_int)
+        sig("segm_add_norm_bwd", [C.POINTER(AddNormArgs)], C.c_int)
+        sig("segm_add_norm_workspace_bytes", [C.c_int64, C.c_int32], C.c_size_t)
         sig("segm_abi_version", [], C.c_int)
         sig("segm_status_string", [C.c_int], C.c_char_p)
 

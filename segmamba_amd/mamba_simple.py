@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import lib as L
+from .add_norm import RMSNorm, layer_norm_fn, rms_norm_fn
 from .linear import linear_cl
 from .selective_scan_interface import MambaInnerCore3, _inner
 
@@ -264,3 +265,37 @@ class Mamba(nn.Module):
                 conv_state.zero_()
                 ssm_state.zero_()
         return conv_state, ssm_state
+
+
+class Block(nn.Module):
+    """The reference package's residual-stacking unit (mamba_simple.py:445-501): Add -> LayerNorm / RMSNorm -> Mixer.
+
+    `forward(hidden_states, residual)` returns (mixer(norm(hidden_states + residual)), hidden_states + residual): the sum is
+    handed on, so that the next block's add, its norm and the optional fp32 copy of the stream are one pass over the tokens.  The
+    first block of a stack gets `residual=None`.  With `fused_add_norm` that pass is `layer_norm_fn` / `rms_norm_fn`
+    (segmamba_amd.add_norm, csrc/add_norm.hip); without it the same steps are ATen calls.  `mixer_cls` and `norm_cls` are called
+    with `dim`; the mixer's forward takes `inference_params`."""
+
+    def __init__(self, dim, mixer_cls, norm_cls=nn.LayerNorm, fused_add_norm=False, residual_in_fp32=False):
+        super().__init__()
+        self.residual_in_fp32 = residual_in_fp32
+        self.fused_add_norm = fused_add_norm
+        self.mixer = mixer_cls(dim)
+        self.norm = norm_cls(dim)
+        if fused_add_norm and not isinstance(self.norm, (nn.LayerNorm, RMSNorm)):
+            raise AssertionError("Only LayerNorm and RMSNorm are supported for fused_add_norm")
+
+    def forward(self, hidden_states, residual=None, inference_params=None):
+        if self.fused_add_norm:
+            fn = rms_norm_fn if isinstance(self.norm, RMSNorm) else layer_norm_fn
+            hidden_states, residual = fn(hidden_states, self.norm.weight, self.norm.bias, residual=residual, prenorm=True,
+                                         residual_in_fp32=self.residual_in_fp32, eps=self.norm.eps)
+        else:
+            residual = hidden_states if residual is None else hidden_states + residual
+            hidden_states = self.norm(residual.to(dtype=self.norm.weight.dtype))
+            if self.residual_in_fp32:
+                residual = residual.to(torch.float32)
+        return self.mixer(hidden_states, inference_params=inference_params), residual
+
+    def allocate_inference_cache(self, batch_size, max_seqlen, dtype=None, **kwargs):
+        return self.mixer.allocate_inference_cache(batch_size, max_seqlen, dtype=dtype, **kwargs)

@@ -3046,6 +3046,145 @@ def window_finish(lib: L.SegmLib, acc: torch.Tensor, count: torch.Tensor, total:
 
 
 # ---------------------------------------------------------------------------------------------------------
+# fused residual add + LayerNorm / RMSNorm (csrc/add_norm.hip)
+# ---------------------------------------------------------------------------------------------------------
+def _add_norm_rows(t, shape, dtypes, like, what: str):
+    """a (M, N) operand of the add + norm entries: its dtype among `dtypes`, on the device of `like`, unit stride along a row and a
+    row stride of at least N, aligned to its element -> the row stride as the entry takes it"""
+    if not isinstance(t, torch.Tensor) or tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{what} must be a tensor of shape {tuple(shape)}, got {getattr(t, 'shape', type(t))}")
+    if t.dtype not in dtypes:
+        raise RuntimeError(f"{what} must be of {' / '.join(str(d) for d in dtypes)}, got {t.dtype}")
+    if like is not None and t.device != like.device:
+        raise RuntimeError(f"{what} must be on {like.device}, got {t.device}")
+    M, N = shape
+    if M == 0:
+        return N
+    if N > 1 and t.stride(1) != 1:
+        raise RuntimeError(f"{what} must have a unit stride along its rows, got strides {t.stride()}")
+    if M > 1 and t.stride(0) < N:
+        raise RuntimeError(f"{what} must have a row stride of at least {N}, got strides {t.stride()}")
+    if t.data_ptr() % t.element_size():
+        raise RuntimeError(f"{what} is not aligned to its element")
+    return t.stride(0) if M > 1 else N
+
+
+def _add_norm_vector(t, N: int, like, what: str, optional: bool = False):
+    """weight / bias / mean / rstd: fp32, contiguous, of N elements, on the device of `like`"""
+    if t is None and optional:
+        return None
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (N,) or t.device != like.device \
+            or not t.is_contiguous():
+        raise RuntimeError(f"{what} must be a contiguous fp32 tensor of {N} elements on {like.device}, "
+                           f"got {getattr(t, 'shape', type(t))} {getattr(t, 'dtype', '')} {getattr(t, 'device', '')}")
+    return t
+
+
+def _add_norm_shape(x, what: str):
+    if not isinstance(x, torch.Tensor) or x.dim() != 2:
+        raise RuntimeError(f"{what}: a 2-D tensor (rows, cols) is required, got {getattr(x, 'shape', type(x))}")
+    M, N = int(x.shape[0]), int(x.shape[1])
+    if not 1 <= N <= L.ADD_NORM_MAX_COLS:
+        raise RuntimeError(f"{what}: 1 .. {L.ADD_NORM_MAX_COLS} columns are supported, got {N}")
+    if M >= 1 << 31:
+        raise RuntimeError(f"{what}: fewer than 2^31 rows are supported, got {M}")
+    return M, N
+
+
+def add_norm_fwd(lib: L.SegmLib, x: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None,
+                 residual: Optional[torch.Tensor] = None, eps: float = 1e-6, rms: bool = False, residual_dtype=None):
+    """s = x + residual in fp32; y = LayerNorm(s) or RMSNorm(s) with weight / bias, in x's dtype -> (y, mean, rstd, residual_out).
+    x (M, N <= 8192) fp32 / fp16 / bf16 and residual (M, N) of x's dtype or fp32: unit stride along a row, any row stride >= N.
+    weight, bias: fp32 (N,).  residual_out = s rounded to the residual's dtype is written when there is a residual, or when
+    `residual_dtype` (x's dtype or fp32) differs from x's dtype; None otherwise (the row saved for the backward is then x).
+    mean (None for rms) and rstd: fp32 (M,).  The statistics come from the unrounded s (reference layernorm.py:65-120)."""
+    what = "add_norm_fwd"
+    M, N = _add_norm_shape(x, what)
+    sx = _add_norm_rows(x, (M, N), tuple(L._DTYPES), None, f"{what}: x")
+    weight = _add_norm_vector(weight, N, x, f"{what}: weight")
+    bias = _add_norm_vector(bias, N, x, f"{what}: bias", optional=True)
+    res_choices = (x.dtype, torch.float32)
+    sres = 0
+    if residual is not None:
+        sres = _add_norm_rows(residual, (M, N), res_choices, x, f"{what}: residual")
+        residual_dtype = residual.dtype
+    elif residual_dtype is not None and residual_dtype not in res_choices:
+        raise RuntimeError(f"{what}: residual_dtype must be {x.dtype} or torch.float32, got {residual_dtype}")
+    y = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    residual_out = None
+    if residual is not None or (residual_dtype is not None and residual_dtype != x.dtype):
+        residual_out = torch.empty((M, N), dtype=residual_dtype, device=x.device)
+    mean = None if rms else torch.empty((M,), dtype=torch.float32, device=x.device)
+    rstd = torch.empty((M,), dtype=torch.float32, device=x.device)
+    if M == 0:
+        return y, mean, rstd, residual_out
+    a = L.AddNormArgs()
+    a.rows, a.cols, a.dtype, a.rms, a.eps = M, N, L.dtype_code(x), int(bool(rms)), float(eps)
+    a.res_dtype = L._DTYPES[residual_dtype] if residual_dtype is not None else a.dtype
+    a.x, a.x_stride, a.y, a.y_stride = x.data_ptr(), sx, y.data_ptr(), N
+    if residual is not None:
+        a.residual, a.residual_stride = residual.data_ptr(), sres
+    if residual_out is not None:
+        a.residual_out, a.residual_out_stride = residual_out.data_ptr(), N
+    a.weight, a.bias, a.mean, a.rstd = weight.data_ptr(), L.fptr(bias), L.fptr(mean), rstd.data_ptr()
+    a.stream = L.stream_handle(x)
+    lib.check(lib.dll.segm_add_norm_fwd(a), what)
+    return y, mean, rstd, residual_out
+
+
+def add_norm_bwd(lib: L.SegmLib, dy: torch.Tensor, x_saved: torch.Tensor, weight: torch.Tensor, mean: Optional[torch.Tensor],
+                 rstd: torch.Tensor, dresidual: Optional[torch.Tensor] = None, has_residual: bool = False, has_bias: bool = False,
+                 rms: bool = False):
+    """The backward of `add_norm_fwd` -> (dx, dweight, dbias, dresidual_in).  dy (M, N) in x's dtype; x_saved (M, N) what the
+    forward kept: residual_out where it wrote one (x's dtype or fp32), x otherwise; mean (None for rms), rstd fp32 (M,);
+    dresidual (M, N) of x_saved's dtype: the gradient that reached residual_out, added to dx.  dx has dy's dtype; dweight and dbias
+    (None without `has_bias`) are fp32 (N,).  dresidual_in, the gradient of the residual, is None without `has_residual`, dx itself
+    where the residual has x's dtype, and dx before its rounding, in fp32, otherwise (reference layernorm.py:293-377)."""
+    what = "add_norm_bwd"
+    M, N = _add_norm_shape(dy, what)
+    sdy = _add_norm_rows(dy, (M, N), tuple(L._DTYPES), None, f"{what}: dy")
+    ssaved = _add_norm_rows(x_saved, (M, N), (dy.dtype, torch.float32), dy, f"{what}: x_saved")
+    weight = _add_norm_vector(weight, N, dy, f"{what}: weight")
+    if not rms:
+        mean = _add_norm_vector(mean, M, dy, f"{what}: mean")
+    rstd = _add_norm_vector(rstd, M, dy, f"{what}: rstd")
+    sdres = 0
+    if dresidual is not None:
+        sdres = _add_norm_rows(dresidual, (M, N), (x_saved.dtype,), dy, f"{what}: dresidual")
+    dx = torch.empty((M, N), dtype=dy.dtype, device=dy.device)
+    dweight = torch.empty((N,), dtype=torch.float32, device=dy.device)
+    dbias = torch.empty((N,), dtype=torch.float32, device=dy.device) if has_bias else None
+    wide = x_saved.dtype != dy.dtype
+    dresidual_in = torch.empty((M, N), dtype=x_saved.dtype, device=dy.device) if has_residual and wide else None
+    if M == 0:
+        dweight.zero_()
+        if dbias is not None:
+            dbias.zero_()
+        return dx, dweight, dbias, (dresidual_in if wide else dx) if has_residual else None
+    a = L.AddNormArgs()
+    a.rows, a.cols, a.dtype, a.res_dtype, a.rms = M, N, L.dtype_code(dy), L.dtype_code(x_saved), int(bool(rms))
+    if wide:
+        a.residual_out, a.residual_out_stride = x_saved.data_ptr(), ssaved
+    else:
+        a.x, a.x_stride = x_saved.data_ptr(), ssaved
+    a.dy, a.dy_stride, a.dx, a.dx_stride = dy.data_ptr(), sdy, dx.data_ptr(), N
+    if dresidual is not None:
+        a.dresidual, a.dresidual_stride = dresidual.data_ptr(), sdres
+    if dresidual_in is not None:
+        a.dresidual_in, a.dresidual_in_stride = dresidual_in.data_ptr(), N
+    a.weight, a.mean, a.rstd = weight.data_ptr(), L.fptr(None if rms else mean), rstd.data_ptr()
+    a.dweight, a.dbias = dweight.data_ptr(), L.fptr(dbias)
+    nbytes = lib.dll.segm_add_norm_workspace_bytes(M, N)
+    if nbytes == 0:
+        raise RuntimeError(f"{what}: the shape {(M, N)} is out of range")
+    workspace = torch.empty(nbytes // 4, dtype=torch.float32, device=dy.device)
+    a.workspace, a.workspace_bytes = workspace.data_ptr(), nbytes
+    a.stream = L.stream_handle(dy)
+    lib.check(lib.dll.segm_add_norm_bwd(a), what)
+    return dx, dweight, dbias, (dresidual_in if wide else dx) if has_residual else None
+
+
+# ---------------------------------------------------------------------------------------------------------
 # device guard
 # ---------------------------------------------------------------------------------------------------------
 # The reference's native ops run under a CUDAGuard on their first tensor's device (selective_scan.cpp:326-327,
@@ -3091,5 +3230,5 @@ for _name in ("scan_fwd", "scan_bwd", "conv1d_fwd", "conv1d_bwd", "conv3d_k3_wgr
               "space_to_depth2", "seg_regions", "edt_sq", "edt_sq_long", "planes_bbox", "border_distances", "border_stats", "sdm_masks", "sdm_compose", "resample_argmax", "ccl_roots", "ccl_sizes", "ccl_select",
               "nonzero_mask_bbox", "crop_stats", "crop_normalize", "zoom", "zoom_labels", "zoom_slices", "zoom_labels_slices", "spline_coefs", "affine_spline3", "affine_labels",
               "zoom_nearest", "gauss_blur", "intensity_stats", "intensity_apply", "window_gather", "window_count", "window_blend",
-              "window_finish"):
+              "window_finish", "add_norm_fwd", "add_norm_bwd"):
     globals()[_name] = _device_guard(globals()[_name])
